@@ -19,9 +19,16 @@ launch stream inside the timed region; peak = 2.5 PFLOP/s dense bf16 MFMA (MI355
 brackets are reported: `launch_ms` / `frac` around the K1 launches alone and `op_ms` / `frac_op` around the
 whole forward op (operand packing + Gram GEMM + K-tiling + K1).  `loss_path` gives the K1 backward launch,
 the backward op (launch + the three gradient GEMMs + scatter) and the share of library GEMMs in it.
-`cpu_baseline` times the reference-structured CPU restatement (oracle/, "port") on the host cores, rank 0,
+A plain run sets up, warms up, times the K steps and prints the line; the roofline / loss_path figures come from
+HIP events inside those timed steps.  `--full` adds what takes work of its own after the timed steps:
+`kernel_launches_per_step` (one extra step under torch.profiler) and `cpu_baseline`, which times the
+reference-structured CPU restatement (oracle/, "port") on the host cores, rank 0,
 N = 1 only: the full training step at B = 16 (BASELINE.json configs[0]) as `value`, plus the loss alone
-(forward + backward at B = 16 / 64, forward at B = 256) - medians, thread count = all host cores.
+(forward + backward at B = 16 / 64, forward at B = 256 with --cpu-full) - medians, thread count = all host cores.
+
+`--dump-outputs DIR` writes what the last timed step hands its caller (rank 0) as .npy files: loss.npy (float64),
+parameters.npy and buffers.npy (float32, the model state the step left; a fixed, seeded sample of the larger tensors).
+Inputs and initial weights are seeded, so two builds run with the same arguments can be compared file for file.
 """
 
 import argparse
@@ -41,6 +48,7 @@ torch = None                    # imported by main() AFTER the launcher decision
 GLOBAL_BATCH = 256
 PEAK_BF16_MFMA = 2.5e15        # dense, FLOP/s (MI355X_MICROARCH.md: ~2.5 PF dense bf16)
 PEAK_F32_MFMA = 157.3e12
+DUMP_SAMPLE = 32768            # --dump-outputs: values kept per tensor (seeded positions; ~17 MB for the whole model)
 
 
 def build(cfg_batch, precision, device, dist_ctx, bert_layers=12, miopen_benchmark=False, train_flags=False):
@@ -73,6 +81,39 @@ def _median(xs):
 
 def _say(msg):
     print(f"[bench] {msg}", file=sys.stderr, flush=True)
+
+
+def dump_outputs(out_dir, trainer, model, loss):
+    """--dump-outputs: the step's loss and the state it left in the model, as a caller of Trainer.training_step receives
+    them.  Parameters are the fp32 values a checkpoint holds (the flat optimizer's master copies, not the bf16 shadows),
+    in named_parameters() order; buffers are the floating-point ones (BatchNorm statistics).  A tensor larger than
+    DUMP_SAMPLE values contributes DUMP_SAMPLE positions drawn with a seed taken from its name."""
+    import zlib
+    import numpy as np
+    master_of = getattr(trainer.optimizer, "master_of", None)
+
+    def sample(named):
+        parts = []
+        for name, t in named:
+            flat = t.detach().reshape(-1)
+            if flat.numel() > DUMP_SAMPLE:
+                pos = np.sort(np.random.default_rng(zlib.crc32(name.encode())).choice(flat.numel(), DUMP_SAMPLE,
+                                                                                    replace=False))
+                flat = flat[torch.from_numpy(pos).to(flat.device)]
+            parts.append(flat.float().cpu())
+        return torch.cat(parts).numpy()
+
+    def fp32(p):
+        m = master_of(p) if master_of else None
+        return p if m is None else m
+
+    params = [(n, fp32(p)) for n, p in model.named_parameters()]
+    buffers = [(n, b) for n, b in model.named_buffers() if b.is_floating_point()]
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "loss.npy"), np.array([float(loss)], dtype=np.float64))
+    np.save(os.path.join(out_dir, "parameters.npy"), sample(params))
+    np.save(os.path.join(out_dir, "buffers.npy"), sample(buffers))
+    _say(f"outputs of the last timed step written to {out_dir}")
 
 
 def cpu_baseline(sample_batch=16, full=False):
@@ -283,8 +324,13 @@ def main():
     ap.add_argument("--lengths", default="words", choices=["words", "mix", "max"],
                     help="words: caption WORD counts ~ U{4..39} (SURVEY.md 8d, the metric's workload); mix: round 1's "
                          "word-PIECE counts ~ U{4..39}; max: every caption at the 97-token limit")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--cpu-full", action="store_true", help="cpu_baseline also runs the loss forward at B = 256 (minutes)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also count the kernel launches of one step and run cpu_baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's loss and model state to DIR/*.npy (rank 0)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip cpu_baseline")
+    ap.add_argument("--cpu-full", action="store_true",
+                    help="with --full: cpu_baseline also runs the loss forward at B = 256 (minutes)")
     ap.add_argument("--bert-layers", type=int, default=12)
     ap.add_argument("--global-batch", type=int, default=GLOBAL_BATCH,
                     help="experiments only: the metric is defined at the default 256")
@@ -373,9 +419,12 @@ def main():
     achieved = mean_flops / (k1_ms * 1e-3) / 1e12 if k1_ms else 0.0
     achieved_op = mean_flops / (k1_op_ms * 1e-3) / 1e12 if k1_op_ms else 0.0
 
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, trainer, model, loss)     # before --full's extra step changes the weights
+
     # kernel launches of one step (outside the timed region; the step floor at small per-GPU batches is launch bound)
     launches = None
-    if rank == 0:
+    if rank == 0 and args.full:
         try:
             from torch.profiler import ProfilerActivity, profile
             with profile(activities=[ProfilerActivity.CUDA]) as tp:
@@ -432,7 +481,7 @@ def main():
             "loss_path": {"k1_bwd_launch_ms": k1_bwd_ms, "k1_bwd_op_ms": k1_bwd_op_ms,
                           "k1_bwd_library_gemm_share": (1.0 - k1_bwd_ms / k1_bwd_op_ms) if (k1_bwd_ms and k1_bwd_op_ms) else None},
         }
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             # free the GPU-side model first; the CPU leg builds its own copy
             rec["cpu_baseline"] = cpu_baseline(full=args.cpu_full)
         os.write(out_fd, (json.dumps(rec) + "\n").encode())

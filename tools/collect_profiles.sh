@@ -7,17 +7,17 @@ OUT="$ROOT/gpurun_out/$TAG"
 mkdir -p "$OUT"
 say() { echo "[collect] $*"; }
 say "ablation library"; make -C gloria-nlp-project_amd/csrc ablate > "$OUT/make_ablate.log" 2>&1
-say "bench default"; timeout -k 10 500 python bench.py > "$OUT/bench.json" 2> "$OUT/bench.err"
-say "bench max lengths"; timeout -k 10 300 python bench.py --lengths max --no-cpu-baseline --steps 5 > "$OUT/bench_max_lengths.json" 2>> "$OUT/bench.err"
-say "bench cfg2 fp32 B=64"; timeout -k 10 300 python bench.py --precision fp32 --global-batch 64 --no-cpu-baseline --steps 5 > "$OUT/bench_cfg2_fp32_b64.json" 2>> "$OUT/bench.err"
+say "bench default"; timeout -k 10 500 python bench.py --full > "$OUT/bench.json" 2> "$OUT/bench.err"
+say "bench max lengths"; timeout -k 10 300 python bench.py --full --lengths max --no-cpu-baseline --steps 5 > "$OUT/bench_max_lengths.json" 2>> "$OUT/bench.err"
+say "bench cfg2 fp32 B=64"; timeout -k 10 300 python bench.py --full --precision fp32 --global-batch 64 --no-cpu-baseline --steps 5 > "$OUT/bench_cfg2_fp32_b64.json" 2>> "$OUT/bench.err"
 for gb in 128 64 32; do
-  say "bench per-GPU batch $gb"; timeout -k 10 300 python bench.py --global-batch $gb --no-cpu-baseline > "$OUT/bench_b$gb.json" 2>> "$OUT/bench.err"
+  say "bench per-GPU batch $gb"; timeout -k 10 300 python bench.py --full --global-batch $gb --no-cpu-baseline > "$OUT/bench_b$gb.json" 2>> "$OUT/bench.err"
 done
-say "bench with the reference's training flags (submit_job.sh:15)"; timeout -k 10 300 python bench.py --train-flags --no-cpu-baseline > "$OUT/bench_train_flags.json" 2>> "$OUT/bench.err"
+say "bench with the reference's training flags (submit_job.sh:15)"; timeout -k 10 300 python bench.py --full --train-flags --no-cpu-baseline > "$OUT/bench_train_flags.json" 2>> "$OUT/bench.err"
 say "forced single-rank RCCL path at 32"
-GLR_FORCE_DIST=1 RANK=0 WORLD_SIZE=1 LOCAL_RANK=0 MASTER_ADDR=127.0.0.1 MASTER_PORT=29571 timeout -k 10 300 python bench.py --global-batch 32 --no-cpu-baseline > "$OUT/bench_b32_forced_dist.json" 2>> "$OUT/bench.err"
+GLR_FORCE_DIST=1 RANK=0 WORLD_SIZE=1 LOCAL_RANK=0 MASTER_ADDR=127.0.0.1 MASTER_PORT=29571 timeout -k 10 300 python bench.py --full --global-batch 32 --no-cpu-baseline > "$OUT/bench_b32_forced_dist.json" 2>> "$OUT/bench.err"
 say "rocprofv3 kernel stats of bench.py"
-(cd /tmp && export TMPDIR=/tmp && timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/prof_bench" -- python3 "$ROOT/bench.py" --steps 5 --warmup 3 --no-cpu-baseline > "$OUT/bench_profiled.json" 2> "$OUT/prof_bench.err")
+(cd /tmp && export TMPDIR=/tmp && timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/prof_bench" -- python3 "$ROOT/bench.py" --full --steps 5 --warmup 3 --no-cpu-baseline > "$OUT/bench_profiled.json" 2> "$OUT/prof_bench.err")
 python tools/step_breakdown.py "$OUT"/prof_bench/*/*_kernel_trace.csv --steps 4 > "$OUT/step_breakdown.txt" 2>&1
 cp "$OUT"/prof_bench/*/*_kernel_stats.csv "$OUT/bench_kernel_stats.csv" 2>/dev/null
 rm -rf "$OUT/prof_bench"
