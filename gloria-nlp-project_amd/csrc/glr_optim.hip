@@ -9,6 +9,13 @@
 //                       same pass: no per-step autocast weight casts, no gradient casts, one launch per dtype group
 //                       instead of ~600 small kernels.  HBM-bound: 4 + 4 + 4 + 2 read, 4 + 4 + 4 + 2 written per
 //                       shadowed parameter.
+// Guarded forms (the `GUARD` instantiations, glr_*_g): the sums of squares also count the non-finite gradient elements
+// of their share and note the first one, glr_step_guard turns that into a per-step skip decision in a small device
+// record (include/glr.h GLR_GUARD_*), and the Adam kernels return without writing anything when the step is skipped -
+// GradScaler's skip of native AMP, decided on the device with no host round trip.  The unguarded instantiations are
+// the code of the plain entry points, unchanged.
+#include <climits>
+
 #include "glr_common.h"
 
 namespace {
@@ -32,22 +39,71 @@ __device__ __forceinline__ void load8(const void* p, int dtype, size_t i, float 
   }
 }
 
-// partial[blockIdx.x] = sum of squares of this block's contiguous share (n is a multiple of 8: buffers are padded)
-__global__ void __launch_bounds__(OPT_NT) k_sumsq(const void* __restrict__ x, int dtype, size_t n, float* __restrict__ partial) {
+// inf / NaN test on the exponent bits (a bf16 value widened to fp32 keeps them: (u & 0x7f80) == 0x7f80 in bf16)
+__device__ __forceinline__ bool non_finite(float x) { return (__float_as_uint(x) & 0x7f800000u) == 0x7f800000u; }
+
+// a thread's count of non-finite elements and the smallest offset among them
+struct BadSeen {
+  long long n = 0, first = LLONG_MAX;
+  __device__ __forceinline__ void see(float x, long long off) {
+    if (non_finite(x)) { ++n; first = off < first ? off : first; }
+  }
+};
+
+__device__ __forceinline__ long long wave_sum_ll(long long v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+__device__ __forceinline__ long long wave_min_ll(long long v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) { const long long u = __shfl_xor(v, o, 64); v = u < v ? u : v; }
+  return v;
+}
+
+// nf[2 b] = non-finite count of block b's share, nf[2 b + 1] = the smallest offset among them (-1: none).  No atomics:
+// every workgroup owns its two slots, like partial[b].
+__device__ __forceinline__ void write_bad(BadSeen bad, long long* __restrict__ nf) {
+  __shared__ long long rn[OPT_NT / 64], rf[OPT_NT / 64];
+  bad.n = wave_sum_ll(bad.n);
+  bad.first = wave_min_ll(bad.first);
+  if ((threadIdx.x & 63) == 0) { rn[threadIdx.x >> 6] = bad.n; rf[threadIdx.x >> 6] = bad.first; }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const long long n = (rn[0] + rn[1]) + (rn[2] + rn[3]);
+    long long f = rf[0] < rf[1] ? rf[0] : rf[1];
+    f = rf[2] < f ? rf[2] : f;
+    f = rf[3] < f ? rf[3] : f;
+    nf[2 * (size_t)blockIdx.x] = n;
+    nf[2 * (size_t)blockIdx.x + 1] = n ? f : -1;
+  }
+}
+
+// partial[blockIdx.x] = sum of squares of this block's contiguous share (n is a multiple of 8: buffers are padded);
+// GUARD: + its non-finite count and first non-finite offset in x
+template <bool GUARD>
+__global__ void __launch_bounds__(OPT_NT) k_sumsq(const void* __restrict__ x, int dtype, size_t n, float* __restrict__ partial,
+                                                  long long* __restrict__ nf) {
   __shared__ float red[OPT_NT / 64];
   const size_t per = ((n / OPT_VEC + gridDim.x - 1) / gridDim.x) * OPT_VEC;
   const size_t lo = (size_t)blockIdx.x * per, hi = lo + per < n ? lo + per : n;
   float s = 0.f;
+  BadSeen bad;
   for (size_t i = lo + (size_t)threadIdx.x * OPT_VEC; i < hi; i += (size_t)OPT_NT * OPT_VEC) {
     float v[8];
     load8(x, dtype, i, v);
 #pragma unroll
     for (int k = 0; k < 8; ++k) s = __builtin_fmaf(v[k], v[k], s);
+    if constexpr (GUARD) {
+#pragma unroll
+      for (int k = 0; k < 8; ++k) bad.see(v[k], (long long)(i + k));
+    }
   }
   s = wave_sum(s);
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
   __syncthreads();
   if (threadIdx.x == 0) partial[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
+  if constexpr (GUARD) write_bad(bad, nf);
 }
 
 // out[0] = sqrt(sum partial), out[1] = clip coefficient (1 when max_norm <= 0)
@@ -66,13 +122,79 @@ __global__ void __launch_bounds__(OPT_NT) k_clip_coef(const float* __restrict__ 
   }
 }
 
+// out[0] = sqrt(sum partial), out[1] = the coefficient - the arithmetic of k_clip_coef, in the same order - and the
+// step's skip decision in rec (include/glr.h GLR_GUARD_*): skipped when ANY element counted by the guarded sums of
+// squares is inf / NaN (GradScaler's test).  Finite elements whose norm overflows are not skipped: coefficient 0 as in
+// k_clip_coef.  One workgroup; thread 0 updates the record.
+__global__ void __launch_bounds__(OPT_NT) k_step_guard(const float* __restrict__ partial, const long long* __restrict__ nf,
+                                                       int n, float max_norm, float* __restrict__ out,
+                                                       long long* __restrict__ rec, long long call) {
+  __shared__ float red[OPT_NT / 64];
+  __shared__ long long rn[OPT_NT / 64], rf[OPT_NT / 64];
+  float s = 0.f;
+  long long cnt = 0, first = LLONG_MAX;          // first: the smallest partial index with a non-finite element
+  for (int i = threadIdx.x; i < n; i += OPT_NT) {
+    s += partial[i];
+    const long long c = nf[2 * (size_t)i];
+    cnt += c;
+    if (c != 0 && i < first) first = i;
+  }
+  s = wave_sum(s);
+  cnt = wave_sum_ll(cnt);
+  first = wave_min_ll(first);
+  if ((threadIdx.x & 63) == 0) { red[threadIdx.x >> 6] = s; rn[threadIdx.x >> 6] = cnt; rf[threadIdx.x >> 6] = first; }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const float norm = sqrtf((red[0] + red[1]) + (red[2] + red[3]));
+    out[0] = norm;
+    out[1] = max_norm > 0.f ? fminf(1.f, max_norm / (norm + 1e-6f)) : 1.f;
+    const long long bad = (rn[0] + rn[1]) + (rn[2] + rn[3]);
+    if (bad == 0) {
+      rec[GLR_GUARD_APPLIED] += 1;
+      rec[GLR_GUARD_CONSECUTIVE] = 0;
+      rec[GLR_GUARD_SKIP] = 0;
+    } else {
+      long long f = rf[0] < rf[1] ? rf[0] : rf[1];
+      f = rf[2] < f ? rf[2] : f;
+      f = rf[3] < f ? rf[3] : f;
+      const long long run = rec[GLR_GUARD_CONSECUTIVE] + 1;
+      rec[GLR_GUARD_SKIPPED] += 1;
+      rec[GLR_GUARD_CONSECUTIVE] = run;
+      rec[GLR_GUARD_SKIP] = 1;
+      rec[GLR_GUARD_LAST_CALL] = call;
+      rec[GLR_GUARD_LAST_COUNT] = bad;
+      rec[GLR_GUARD_LAST_PARTIAL] = f;
+      rec[GLR_GUARD_LAST_OFFSET] = nf[2 * (size_t)f + 1];
+      if (run > rec[GLR_GUARD_LONGEST]) rec[GLR_GUARD_LONGEST] = run;
+    }
+  }
+}
+
+// GUARD: nothing is written when the guard skipped this step; the bias corrections come from the host-built table at
+// the applied-step count the guard has just advanced (bias[2 (t - 1)] = 1 - b1^t, bias[2 (t - 1) + 1] = sqrt(1 - b2^t)),
+// i.e. the very floats the unguarded launch wrappers pass as bc1 / bc2_sqrt
+__device__ __forceinline__ bool guard_skip(const long long* __restrict__ rec, const float* __restrict__ bias, int bias_cap,
+                                           float& bc1, float& bc2_sqrt) {
+  if (rec[GLR_GUARD_SKIP] != 0) return true;
+  long long t = rec[GLR_GUARD_APPLIED];
+  t = t < 1 ? 1 : (t > bias_cap ? bias_cap : t);
+  bc1 = bias[2 * (t - 1)];
+  bc2_sqrt = bias[2 * (t - 1) + 1];
+  return false;
+}
+
+template <bool GUARD>
 __global__ void __launch_bounds__(OPT_NT) k_adam(float* __restrict__ master, float* __restrict__ m, float* __restrict__ v,
                                                  const void* __restrict__ grad, int grad_dtype,
                                                  unsigned short* __restrict__ shadow, size_t n, float lr, float b1, float b2,
                                                  float eps, float wd, float bc1, float bc2_sqrt,
-                                                 const float* __restrict__ clip) {
+                                                 const float* __restrict__ clip, const long long* __restrict__ rec,
+                                                 const float* __restrict__ bias, int bias_cap) {
   const size_t i = ((size_t)blockIdx.x * OPT_NT + threadIdx.x) * OPT_VEC;
   if (i >= n) return;
+  if constexpr (GUARD) {
+    if (guard_skip(rec, bias, bias_cap, bc1, bc2_sqrt)) return;
+  }
   const float c = clip ? clip[1] : 1.f;
   float g[8], p[8], a[8], b[8];
   load8(grad, grad_dtype, i, g);
@@ -115,12 +237,15 @@ __device__ __forceinline__ float ld1(const void* p, int dtype, size_t i) {
   return dtype == GLR_BF16 ? bf2f(reinterpret_cast<const unsigned short*>(p)[i]) : reinterpret_cast<const float*>(p)[i];
 }
 
+// GUARD: non-finite offsets are element offsets inside the chunk (0 .. count - 1)
+template <bool GUARD>
 __global__ void __launch_bounds__(OPT_NT) k_sumsq_mt(const ChunkEnt* __restrict__ chunk, const unsigned long long* __restrict__ gptr,
-                                                     int dtype, float* __restrict__ partial) {
+                                                     int dtype, float* __restrict__ partial, long long* __restrict__ nf) {
   __shared__ float red[OPT_NT / 64];
   const ChunkEnt e = chunk[blockIdx.x];
   const void* g = reinterpret_cast<const void*>(gptr[e.param]);
   float s = 0.f;
+  BadSeen bad;
   if (g != nullptr) {
     const int nv = e.count & ~7;
     for (int i = threadIdx.x * OPT_VEC; i < nv; i += OPT_NT * OPT_VEC) {
@@ -128,23 +253,37 @@ __global__ void __launch_bounds__(OPT_NT) k_sumsq_mt(const ChunkEnt* __restrict_
       load8(g, dtype, (size_t)e.poff + i, v);
 #pragma unroll
       for (int k = 0; k < 8; ++k) s = __builtin_fmaf(v[k], v[k], s);
+      if constexpr (GUARD) {
+#pragma unroll
+        for (int k = 0; k < 8; ++k) bad.see(v[k], i + k);
+      }
     }
-    for (int i = nv + threadIdx.x; i < e.count; i += OPT_NT) { const float x = ld1(g, dtype, (size_t)e.poff + i); s = __builtin_fmaf(x, x, s); }
+    for (int i = nv + threadIdx.x; i < e.count; i += OPT_NT) {
+      const float x = ld1(g, dtype, (size_t)e.poff + i);
+      s = __builtin_fmaf(x, x, s);
+      if constexpr (GUARD) bad.see(x, i);
+    }
   }
   s = wave_sum(s);
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
   __syncthreads();
   if (threadIdx.x == 0) partial[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
+  if constexpr (GUARD) write_bad(bad, nf);
 }
 
+template <bool GUARD>
 __global__ void __launch_bounds__(OPT_NT) k_adam_mt(const ChunkEnt* __restrict__ chunk, const unsigned long long* __restrict__ gptr,
                                                     int grad_dtype, float* __restrict__ master, float* __restrict__ m,
                                                     float* __restrict__ v, unsigned short* __restrict__ shadow, float lr,
                                                     float b1, float b2, float eps, float wd, float bc1, float bc2_sqrt,
-                                                    const float* __restrict__ clip) {
+                                                    const float* __restrict__ clip, const long long* __restrict__ rec,
+                                                    const float* __restrict__ bias, int bias_cap) {
   const ChunkEnt e = chunk[blockIdx.x];
   const void* gp = reinterpret_cast<const void*>(gptr[e.param]);
   if (gp == nullptr) return;
+  if constexpr (GUARD) {
+    if (guard_skip(rec, bias, bias_cap, bc1, bc2_sqrt)) return;
+  }
   const float c = clip ? clip[1] : 1.f;
   const float step = lr / bc1;
   // chunks start 8-aligned in the flat buffers (parameters are padded to 8) and 8-aligned inside the parameter
@@ -219,8 +358,18 @@ extern "C" int glr_sumsq_mt(const void* chunk_table, int n_chunks, const uint64_
                             void* stream) {
   if (!chunk_table || !grad_ptrs || !partial || n_chunks <= 0) return GLR_EINVAL;
   if (dtype != GLR_F32 && dtype != GLR_BF16) return GLR_EDTYPE;
-  hipLaunchKernelGGL(k_sumsq_mt, dim3(n_chunks), dim3(OPT_NT), 0, (hipStream_t)stream, (const ChunkEnt*)chunk_table,
-                     (const unsigned long long*)grad_ptrs, dtype, partial);
+  hipLaunchKernelGGL(k_sumsq_mt<false>, dim3(n_chunks), dim3(OPT_NT), 0, (hipStream_t)stream, (const ChunkEnt*)chunk_table,
+                     (const unsigned long long*)grad_ptrs, dtype, partial, nullptr);
+  GLR_CHECK_LAUNCH();
+  return GLR_OK;
+}
+
+extern "C" int glr_sumsq_mt_g(const void* chunk_table, int n_chunks, const uint64_t* grad_ptrs, int dtype, float* partial,
+                              int64_t* nonfinite, void* stream) {
+  if (!chunk_table || !grad_ptrs || !partial || !nonfinite || n_chunks <= 0) return GLR_EINVAL;
+  if (dtype != GLR_F32 && dtype != GLR_BF16) return GLR_EDTYPE;
+  hipLaunchKernelGGL(k_sumsq_mt<true>, dim3(n_chunks), dim3(OPT_NT), 0, (hipStream_t)stream, (const ChunkEnt*)chunk_table,
+                     (const unsigned long long*)grad_ptrs, dtype, partial, (long long*)nonfinite);
   GLR_CHECK_LAUNCH();
   return GLR_OK;
 }
@@ -231,9 +380,26 @@ extern "C" int glr_adam_step_mt(const void* chunk_table, int n_chunks, const uin
   if (!chunk_table || !grad_ptrs || !master || !exp_avg || !exp_avg_sq || n_chunks <= 0 || step < 1) return GLR_EINVAL;
   if (grad_dtype != GLR_F32 && grad_dtype != GLR_BF16) return GLR_EDTYPE;
   const float bc1 = 1.f - powf(beta1, (float)step), bc2 = 1.f - powf(beta2, (float)step);
-  hipLaunchKernelGGL(k_adam_mt, dim3(n_chunks), dim3(OPT_NT), 0, (hipStream_t)stream, (const ChunkEnt*)chunk_table,
+  hipLaunchKernelGGL(k_adam_mt<false>, dim3(n_chunks), dim3(OPT_NT), 0, (hipStream_t)stream, (const ChunkEnt*)chunk_table,
                      (const unsigned long long*)grad_ptrs, grad_dtype, master, exp_avg, exp_avg_sq,
-                     (unsigned short*)shadow_bf16, lr, beta1, beta2, eps, weight_decay, bc1, sqrtf(bc2), clip);
+                     (unsigned short*)shadow_bf16, lr, beta1, beta2, eps, weight_decay, bc1, sqrtf(bc2), clip, nullptr,
+                     nullptr, 0);
+  GLR_CHECK_LAUNCH();
+  return GLR_OK;
+}
+
+extern "C" int glr_adam_step_mt_g(const void* chunk_table, int n_chunks, const uint64_t* grad_ptrs, int grad_dtype,
+                                  float* master, float* exp_avg, float* exp_avg_sq, void* shadow_bf16, float lr, float beta1,
+                                  float beta2, float eps, float weight_decay, const float* bias_table, int bias_capacity,
+                                  const int64_t* record, const float* clip, void* stream) {
+  if (!chunk_table || !grad_ptrs || !master || !exp_avg || !exp_avg_sq || !bias_table || !record || n_chunks <= 0 ||
+      bias_capacity < 1)
+    return GLR_EINVAL;
+  if (grad_dtype != GLR_F32 && grad_dtype != GLR_BF16) return GLR_EDTYPE;
+  hipLaunchKernelGGL(k_adam_mt<true>, dim3(n_chunks), dim3(OPT_NT), 0, (hipStream_t)stream, (const ChunkEnt*)chunk_table,
+                     (const unsigned long long*)grad_ptrs, grad_dtype, master, exp_avg, exp_avg_sq,
+                     (unsigned short*)shadow_bf16, lr, beta1, beta2, eps, weight_decay, 1.f, 1.f, clip,
+                     (const long long*)record, bias_table, bias_capacity);
   GLR_CHECK_LAUNCH();
   return GLR_OK;
 }
@@ -247,7 +413,17 @@ extern "C" int glr_sumsq_blocks(long long n) {
 extern "C" int glr_sumsq_partial(const void* x, int dtype, long long n, float* partial, void* stream) {
   if (!x || !partial || n <= 0 || n % OPT_VEC != 0) return GLR_EINVAL;
   if (dtype != GLR_F32 && dtype != GLR_BF16) return GLR_EDTYPE;
-  hipLaunchKernelGGL(k_sumsq, dim3(glr_sumsq_blocks(n)), dim3(OPT_NT), 0, (hipStream_t)stream, x, dtype, (size_t)n, partial);
+  hipLaunchKernelGGL(k_sumsq<false>, dim3(glr_sumsq_blocks(n)), dim3(OPT_NT), 0, (hipStream_t)stream, x, dtype, (size_t)n,
+                     partial, nullptr);
+  GLR_CHECK_LAUNCH();
+  return GLR_OK;
+}
+
+extern "C" int glr_sumsq_partial_g(const void* x, int dtype, long long n, float* partial, int64_t* nonfinite, void* stream) {
+  if (!x || !partial || !nonfinite || n <= 0 || n % OPT_VEC != 0) return GLR_EINVAL;
+  if (dtype != GLR_F32 && dtype != GLR_BF16) return GLR_EDTYPE;
+  hipLaunchKernelGGL(k_sumsq<true>, dim3(glr_sumsq_blocks(n)), dim3(OPT_NT), 0, (hipStream_t)stream, x, dtype, (size_t)n,
+                     partial, (long long*)nonfinite);
   GLR_CHECK_LAUNCH();
   return GLR_OK;
 }
@@ -259,6 +435,15 @@ extern "C" int glr_clip_coef(const float* partial, int n_partial, float max_norm
   return GLR_OK;
 }
 
+extern "C" int glr_step_guard(const float* partial, const int64_t* nonfinite, int n_partial, float max_norm, float* out,
+                              int64_t* record, long long call_index, void* stream) {
+  if (!partial || !nonfinite || !out || !record || n_partial <= 0) return GLR_EINVAL;
+  hipLaunchKernelGGL(k_step_guard, dim3(1), dim3(OPT_NT), 0, (hipStream_t)stream, partial, (const long long*)nonfinite,
+                     n_partial, max_norm, out, (long long*)record, call_index);
+  GLR_CHECK_LAUNCH();
+  return GLR_OK;
+}
+
 extern "C" int glr_adam_step(float* master, float* exp_avg, float* exp_avg_sq, const void* grad, int grad_dtype,
                              void* shadow_bf16, long long n, float lr, float beta1, float beta2, float eps,
                              float weight_decay, int step, const float* clip, void* stream) {
@@ -266,9 +451,37 @@ extern "C" int glr_adam_step(float* master, float* exp_avg, float* exp_avg_sq, c
   if (grad_dtype != GLR_F32 && grad_dtype != GLR_BF16) return GLR_EDTYPE;
   const float bc1 = 1.f - powf(beta1, (float)step), bc2 = 1.f - powf(beta2, (float)step);
   const size_t threads = (size_t)n / OPT_VEC;
-  hipLaunchKernelGGL(k_adam, dim3((unsigned)((threads + OPT_NT - 1) / OPT_NT)), dim3(OPT_NT), 0, (hipStream_t)stream,
+  hipLaunchKernelGGL(k_adam<false>, dim3((unsigned)((threads + OPT_NT - 1) / OPT_NT)), dim3(OPT_NT), 0, (hipStream_t)stream,
                      master, exp_avg, exp_avg_sq, grad, grad_dtype, (unsigned short*)shadow_bf16, (size_t)n, lr, beta1,
-                     beta2, eps, weight_decay, bc1, sqrtf(bc2), clip);
+                     beta2, eps, weight_decay, bc1, sqrtf(bc2), clip, nullptr, nullptr, 0);
   GLR_CHECK_LAUNCH();
+  return GLR_OK;
+}
+
+extern "C" int glr_adam_step_g(float* master, float* exp_avg, float* exp_avg_sq, const void* grad, int grad_dtype,
+                               void* shadow_bf16, long long n, float lr, float beta1, float beta2, float eps,
+                               float weight_decay, const float* bias_table, int bias_capacity, const int64_t* record,
+                               const float* clip, void* stream) {
+  if (!master || !exp_avg || !exp_avg_sq || !grad || !bias_table || !record || n <= 0 || n % OPT_VEC != 0 ||
+      bias_capacity < 1)
+    return GLR_EINVAL;
+  if (grad_dtype != GLR_F32 && grad_dtype != GLR_BF16) return GLR_EDTYPE;
+  const size_t threads = (size_t)n / OPT_VEC;
+  hipLaunchKernelGGL(k_adam<true>, dim3((unsigned)((threads + OPT_NT - 1) / OPT_NT)), dim3(OPT_NT), 0, (hipStream_t)stream,
+                     master, exp_avg, exp_avg_sq, grad, grad_dtype, (unsigned short*)shadow_bf16, (size_t)n, lr, beta1,
+                     beta2, eps, weight_decay, 1.f, 1.f, clip, (const long long*)record, bias_table, bias_capacity);
+  GLR_CHECK_LAUNCH();
+  return GLR_OK;
+}
+
+// host only: the bias corrections of steps 1 .. capacity by the expressions of the launch wrappers above, so that the
+// guarded kernels use bitwise the floats the unguarded ones are handed
+extern "C" int glr_adam_bias_table(float beta1, float beta2, int capacity, float* out) {
+  if (!out || capacity < 1) return GLR_EINVAL;
+  for (int step = 1; step <= capacity; ++step) {
+    const float bc1 = 1.f - powf(beta1, (float)step), bc2 = 1.f - powf(beta2, (float)step);
+    out[2 * (size_t)(step - 1)] = bc1;
+    out[2 * (size_t)(step - 1) + 1] = sqrtf(bc2);
+  }
   return GLR_OK;
 }

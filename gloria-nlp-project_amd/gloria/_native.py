@@ -53,6 +53,14 @@ SYMBOLS = {
     "glr_clip_coef": (c_int, [c_void_p, c_int, c_float, c_void_p, c_void_p]),
     "glr_adam_step": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, ctypes.c_longlong, c_float,
                               c_float, c_float, c_float, c_float, c_int, c_void_p, c_void_p]),
+    "glr_sumsq_partial_g": (c_int, [c_void_p, c_int, ctypes.c_longlong, c_void_p, c_void_p, c_void_p]),
+    "glr_sumsq_mt_g": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
+    "glr_step_guard": (c_int, [c_void_p, c_void_p, c_int, c_float, c_void_p, c_void_p, ctypes.c_longlong, c_void_p]),
+    "glr_adam_step_g": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, ctypes.c_longlong, c_float,
+                                c_float, c_float, c_float, c_float, c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
+    "glr_adam_step_mt_g": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_float,
+                                   c_float, c_float, c_float, c_float, c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
+    "glr_adam_bias_table": (c_int, [c_float, c_float, c_int, c_void_p]),
     "glr_bn_workspace_floats": (c_int, [ctypes.c_longlong, c_int]),
     "glr_bn_act_fwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, ctypes.c_longlong, c_int, c_float, c_float, c_int,
                                c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p]),

@@ -149,6 +149,18 @@ class GLoRIA(nn.Module):
             return False
         return self.text_encoder.enable_graph(caption_ids, attention_mask, token_type_ids, autocast_dtype, warmup)
 
+    def disable_graphs(self):
+        """drop both captured encoder graphs: the following steps run the encoders eagerly.  Returns True when a graph
+        was active (the trainer's non-finite guard, gloria/nonfinite.py: a skipped step may be a broken replay)."""
+        active = self._img_graph is not None or getattr(self.text_encoder, "_graph", None) is not None
+        object.__setattr__(self, "_img_graph", None)
+        self._img_graph_shape = None
+        if getattr(self.text_encoder, "_graph", None) is not None:
+            object.__setattr__(self.text_encoder, "_graph", None)
+            self.text_encoder._graph_key = None
+            self.text_encoder._graph_rng = None
+        return active
+
     def image_encoder_forward(self, imgs):
         if (self._img_graph is not None and self.training and torch.is_grad_enabled()
                 and (tuple(imgs.shape), imgs.dtype) == self._img_graph_shape):

@@ -15,15 +15,21 @@ and 7 ms on one MI355X, which is what bounds a data-parallel rank at 32 pairs pe
   * the gradient norm of clip_grad_norm_ is two launches over the flat gradient buffers, its coefficient never
     leaves the device and is applied inside the Adam kernel;
   * zero_grad is one memset per flat buffer; the flat gradient buffers are the all-reduce buckets of the
-    data-parallel reducer (gloria.dist.GradReducer.from_flat).
+    data-parallel reducer (gloria.dist.GradReducer.from_flat);
+  * a step whose gradients hold any inf / NaN element is skipped on the device, as native AMP's GradScaler skips it:
+    the norm kernels count non-finite elements, a one-workgroup guard (in place of the clip-coefficient launch) writes
+    the skip decision and the applied-step count into a small device record, and the Adam kernels write nothing on a
+    skipped step (gloria/nonfinite.py reads the record; the applied count is Adam's step `t`).
 
 Numerics are those of the AMP recipe: bf16(master) is exactly what autocast's cast hands the forward, and the fp32
 Adam update runs on the masters.
 """
 
+import numpy as np
 import torch
 
 from . import _native as N
+from . import nonfinite as NF
 
 
 def _storage_flat(t):
@@ -162,11 +168,19 @@ class ShadowAdam(torch.optim.Optimizer):
                        for pl, sh in (([p for p in rev if id(p) in shadow_ids], True),
                                       ([p for p in rev if id(p) not in shadow_ids], False)) if pl]
         self.max_grad_norm = float(max_grad_norm) if max_grad_norm else 0.0
-        self.t = 0
         L = N.lib()
         self._nblocks = [L.glr_sumsq_blocks(g.n) if self.flat_grads else g.n_chunks for g in self.groups]
         self._partial = torch.zeros(sum(self._nblocks), dtype=torch.float32, device=dev)
+        self._nonfinite = torch.zeros(2 * sum(self._nblocks), dtype=torch.int64, device=dev)   # per partial: count, first
         self.clip_state = torch.zeros(2, dtype=torch.float32, device=dev)          # [norm, coefficient] of the last step
+        # the guard's record (include/glr.h GLR_GUARD_*): applied steps (Adam's t - the truth), skip counters, the first
+        # non-finite element of the last skipped step
+        self.record = torch.zeros(NF.RECORD_WORDS, dtype=torch.int64, device=dev)
+        self.calls = 0                           # step() calls: the call index the guard notes for a skipped step
+        self._bias, self._bias_cap, self._bias_betas = None, 0, None
+        # where each partial sum comes from (host only: NF.locate)
+        self.layout = [NF.group_layout([p.numel() for p in g.params], nblocks=nb if self.flat_grads else None,
+                                       chunk=None if self.flat_grads else CHUNK) for g, nb in zip(self.groups, self._nblocks)]
         for g in self.groups:                     # per-parameter views of the moments: the stock state_dict layout
             for i, p in enumerate(g.params):
                 self.state[p] = {"step": torch.zeros((), dtype=torch.float32), "exp_avg": g.view(g.exp_avg, i),
@@ -180,34 +194,67 @@ class ShadowAdam(torch.optim.Optimizer):
             for p in g.params:
                 p.grad = None
 
+    def _bias_table(self, b1, b2):
+        """device table of Adam's bias corrections for steps 1 .. capacity (glr_adam_bias_table: the host expressions of
+        the plain launch wrappers, so the guarded kernels compute bitwise what they would).  The applied-step count never
+        exceeds the call count; the table doubles before the calls reach its capacity and is rebuilt when the betas
+        change."""
+        if self._bias is None or self.calls > self._bias_cap or self._bias_betas != (b1, b2):
+            cap = max(self._bias_cap, 1024)
+            while cap < self.calls:
+                cap *= 2
+            host = np.zeros(2 * cap, dtype=np.float32)
+            N.check(N.lib().glr_adam_bias_table(b1, b2, cap, host.ctypes.data), "glr_adam_bias_table")
+            self._bias = N.upload(host, self.record.device)       # stream-ordered before the launches that read it
+            self._bias_cap, self._bias_betas = cap, (b1, b2)
+        return self._bias
+
     @torch.no_grad()
     def step(self, closure=None):
         L, st = N.lib(), N.stream()
+        self.calls += 1
         o = 0
         for g, nb in zip(self.groups, self._nblocks):
             if self.flat_grads:
-                N.check(L.glr_sumsq_partial(N.ptr(g.grad), N.dtype_code(g.gdt), g.n, N.ptr(self._partial[o:]), st),
-                        "glr_sumsq_partial")
+                N.check(L.glr_sumsq_partial_g(N.ptr(g.grad), N.dtype_code(g.gdt), g.n, N.ptr(self._partial[o:]),
+                                              N.ptr(self._nonfinite[2 * o:]), st), "glr_sumsq_partial_g")
             else:
                 g.stage_grad_pointers()
-                N.check(L.glr_sumsq_mt(N.ptr(g.table), g.n_chunks, N.ptr(g.ptr_dev), N.dtype_code(g.gdt),
-                                       N.ptr(self._partial[o:]), st), "glr_sumsq_mt")
+                N.check(L.glr_sumsq_mt_g(N.ptr(g.table), g.n_chunks, N.ptr(g.ptr_dev), N.dtype_code(g.gdt),
+                                         N.ptr(self._partial[o:]), N.ptr(self._nonfinite[2 * o:]), st), "glr_sumsq_mt_g")
             o += nb
-        N.check(L.glr_clip_coef(N.ptr(self._partial), o, self.max_grad_norm, N.ptr(self.clip_state), st), "glr_clip_coef")
-        self.t += 1
+        N.check(L.glr_step_guard(N.ptr(self._partial), N.ptr(self._nonfinite), o, self.max_grad_norm,
+                                 N.ptr(self.clip_state), N.ptr(self.record), self.calls, st), "glr_step_guard")
         pg = self.param_groups[0]
-        hyper = (float(pg["lr"]), float(pg["betas"][0]), float(pg["betas"][1]), float(pg["eps"]),
-                 float(pg["weight_decay"]), self.t, N.ptr(self.clip_state), st)
+        b1, b2 = float(pg["betas"][0]), float(pg["betas"][1])
+        bias = self._bias_table(b1, b2)
+        hyper = (float(pg["lr"]), b1, b2, float(pg["eps"]), float(pg["weight_decay"]), N.ptr(bias), self._bias_cap,
+                 N.ptr(self.record), N.ptr(self.clip_state), st)
         for g in self.groups:
             if self.flat_grads:
-                N.check(L.glr_adam_step(N.ptr(g.master), N.ptr(g.exp_avg), N.ptr(g.exp_avg_sq), N.ptr(g.grad),
-                                        N.dtype_code(g.gdt), N.ptr(g.shadow_buf), g.n, *hyper), "glr_adam_step")
+                N.check(L.glr_adam_step_g(N.ptr(g.master), N.ptr(g.exp_avg), N.ptr(g.exp_avg_sq), N.ptr(g.grad),
+                                          N.dtype_code(g.gdt), N.ptr(g.shadow_buf), g.n, *hyper), "glr_adam_step_g")
             else:
-                N.check(L.glr_adam_step_mt(N.ptr(g.table), g.n_chunks, N.ptr(g.ptr_dev), N.dtype_code(g.gdt),
-                                           N.ptr(g.master), N.ptr(g.exp_avg), N.ptr(g.exp_avg_sq), N.ptr(g.shadow_buf),
-                                           *hyper), "glr_adam_step_mt")
-        for s in self.state.values():
-            s["step"] = torch.tensor(float(self.t))
+                N.check(L.glr_adam_step_mt_g(N.ptr(g.table), g.n_chunks, N.ptr(g.ptr_dev), N.dtype_code(g.gdt),
+                                             N.ptr(g.master), N.ptr(g.exp_avg), N.ptr(g.exp_avg_sq), N.ptr(g.shadow_buf),
+                                             *hyper), "glr_adam_step_mt_g")
+
+    # ---------------------------------------------------------------- the guard's record
+    @property
+    def t(self):
+        """applied (not skipped) steps: the device record's count, read with a sync"""
+        return int(self.record[NF.APPLIED])
+
+    @t.setter
+    def t(self, value):
+        self.record[NF.APPLIED] = int(value)
+        self.calls = max(self.calls, int(value))
+
+    def locate(self, partial_index, offset):
+        """(parameter, element in its memory order) of the non-finite element a guard record names; (None, None) for
+        padding"""
+        gi, i, e = NF.locate(self.layout, partial_index, offset)
+        return (None, None) if i is None else (self.groups[gi].params[i], e)
 
     # ---------------------------------------------------------------- checkpoints: fp32 masters, stock layout
     def master_of(self, p):
@@ -231,6 +278,7 @@ class ShadowAdam(torch.optim.Optimizer):
         """stock layout over `all_params` (the reference optimizer's parameter list): index = position of the parameter
         in the model's registration order; parameters this optimizer leaves out simply have no state entry"""
         own = {id(p) for grp in self.param_groups for p in grp["params"]}
+        self._sync_step()
         state = {i: {k: (v.clone() if torch.is_tensor(v) else v) for k, v in self.state[p].items()}
                  for i, p in enumerate(self.all_params) if id(p) in own}
         grp = {k: v for k, v in self.param_groups[0].items() if k != "params"}
@@ -265,12 +313,16 @@ class ShadowAdam(torch.optim.Optimizer):
         if len(steps) > 1:
             raise ValueError(f"optimizer state holds different step counts {sorted(steps)}: the flat Adam keeps one")
         if steps:
-            self.t = steps.pop()
+            self.t = steps.pop()                  # written to the device record: the guarded Adam reads it there
         for grp, src in zip(self.param_groups, state_dict["param_groups"]):
             for k in ("lr", "betas", "eps", "weight_decay"):
                 grp[k] = src[k]
+        self._sync_step()
+
+    def _sync_step(self):
+        t = torch.tensor(float(self.t))
         for s in self.state.values():
-            s["step"] = torch.tensor(float(self.t))
+            s["step"] = t.clone()
 
 
 def shadow_parameter_ids(model):

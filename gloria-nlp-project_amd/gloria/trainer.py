@@ -10,10 +10,12 @@ import time
 
 import torch
 
+from . import nonfinite as NF
+
 
 class Trainer:
     def __init__(self, cfg, device="cuda", precision=None, dist_ctx=None, log_path=None, miopen_benchmark=False,
-                 sync_bn=False, flat_optimizer=None, graph_image_encoder=None, graph_text_encoder=None):
+                 sync_bn=False, flat_optimizer=None, graph_image_encoder=None, graph_text_encoder=None, nonfinite=None):
         self.cfg = cfg
         self.device = torch.device(device)
         prec = precision if precision is not None else cfg.lightning.trainer.precision
@@ -58,6 +60,12 @@ class Trainer:
             flat_optimizer = os.environ.get("GLR_FLAT_OPTIMIZER", "1") != "0"
         self.flat_optimizer = bool(flat_optimizer) and self.device.type == "cuda" and self.autocast_dtype is not None \
             and cfg.train.optimizer.name == "Adam"
+        # steps whose gradients hold an inf / NaN element are skipped (native AMP's GradScaler behaviour, which the
+        # reference trains under); 'skip' reports them and goes on, 'raise' ends the run (gloria/nonfinite.py).
+        # GLR_NONFINITE=skip / raise
+        self.nonfinite = NF.resolve_mode(nonfinite)
+        self.monitor = None
+        self._record = None
 
     GRAPH_MAX_BATCH = 128
 
@@ -99,7 +107,85 @@ class Trainer:
                 self.reducer = GradReducer.from_flat(self.optimizer.groups, self.dist, overlap=self.reducer_overlap)
             else:
                 self.reducer = GradReducer(self.params, self.dist)      # grads become views of flat buckets
+        self._setup_nonfinite(model)
         return model
+
+    # ------------------------------------------------------------------ non-finite gradients (gloria/nonfinite.py)
+    def _setup_nonfinite(self, model):
+        # the record of applied / skipped steps: the flat optimizer's guard writes its own on the device; the stock path
+        # keeps the same layout up to date with a few tensor ops per step (_stock_guard)
+        if self.flat:
+            self._record = self.optimizer.record
+        else:
+            self._record = torch.zeros(NF.RECORD_WORDS, dtype=torch.int64, device=self.device)
+            self._found_inf = torch.zeros((), dtype=torch.float32, device=self.device)   # GradScaler's shapes
+            self._unit = torch.ones((), dtype=torch.float32, device=self.device)
+        self._pinned = None
+        self._names = {id(p): n for n, p in model.named_parameters()}
+        self._poller = NF.Poller(self._snapshot)
+        self.monitor = NF.Monitor(self.nonfinite, describe=self._describe,
+                                  drop_graphs=getattr(model.gloria, "disable_graphs", None), log=self._log)
+
+    def _snapshot(self):
+        if self._record.is_cuda:
+            if self._pinned is None:
+                self._pinned = torch.zeros(NF.RECORD_WORDS, dtype=torch.int64).pin_memory()
+            self._pinned.copy_(self._record, non_blocking=True)
+            ev = torch.cuda.Event()
+            ev.record()
+            return _Snapshot(ev, self._pinned)
+        return _Snapshot(None, self._record.clone())
+
+    def _describe(self, partial, offset):
+        if not self.flat:
+            return None, None
+        p, e = self.optimizer.locate(partial, offset)
+        if p is None:
+            return None, None
+        return self._names.get(id(p)), NF.unravel(tuple(p.shape), p.stride(), e)
+
+    def _stock_guard(self):
+        """stock optimizer path: GradScaler's element-wise test (unit scale: the gradients stay bitwise as they are) before
+        clipping; fused Adam reads the flag (`found_inf`), skips the update and rolls its step counts back on the
+        device.  Other optimizers (and a CPU device) are skipped from the host.  Returns False when step() must not run."""
+        grads = [p.grad for p in self.params if p.grad is not None]
+        if not grads:
+            return True
+        found = self._found_inf.zero_()
+        if self.device.type == "cuda":
+            torch._amp_foreach_non_finite_check_and_unscale_(grads, found, self._unit)
+        else:
+            found.fill_(0.0 if all(bool(torch.isfinite(g).all()) for g in grads) else 1.0)
+        b = found.to(torch.int64)
+        r = self._record
+        r[NF.APPLIED:NF.APPLIED + 1].add_(1 - b)
+        r[NF.SKIPPED:NF.SKIPPED + 1].add_(b)
+        r[NF.CONSECUTIVE:NF.CONSECUTIVE + 1].add_(1).mul_(b)
+        r[NF.SKIP:NF.SKIP + 1].copy_(b)
+        r[NF.LAST_CALL:NF.LAST_CALL + 1].mul_(1 - b).add_(b * (self.global_step + 1))
+        r[NF.LAST_COUNT:NF.LAST_OFFSET + 1].mul_(1 - b).sub_(b)      # count and location unknown here: -1
+        torch.maximum(r[NF.LONGEST:NF.LONGEST + 1], r[NF.CONSECUTIVE:NF.CONSECUTIVE + 1], out=r[NF.LONGEST:NF.LONGEST + 1])
+        if self.device.type == "cuda" and self.optimizer.defaults.get("fused"):
+            self.optimizer.found_inf = found
+            return True
+        return not bool(found)
+
+    def _poll_nonfinite(self, now=False):
+        """every POLL_EVERY steps: act on the record copied POLL_EVERY steps ago; now=True (the existing sync points):
+        act on the current record"""
+        if self.monitor is None:
+            return
+        if now:
+            self._poller.drop_pending()
+            rec = self._record.tolist()
+        else:
+            rec = self._poller.at_step(self.global_step)
+        self.monitor.act(rec, self.global_step)
+
+    @property
+    def skipped_steps(self):
+        """optimizer steps skipped for non-finite gradients so far (reads the device record: a sync)"""
+        return 0 if self._record is None else int(self._record[NF.SKIPPED])
 
     def to_device(self, batch):
         out = {}
@@ -136,10 +222,13 @@ class Trainer:
         else:
             self.optimizer.zero_grad(set_to_none=True)
             loss.backward()
+        run = True if self.flat else self._stock_guard()       # the flat optimizer guards inside its step
         if self.clip and not self.flat:       # the flat optimizer clips inside its step (post-reduce global norm)
             torch.nn.utils.clip_grad_norm_(self.params, self.clip)
-        self.optimizer.step()
+        if run:
+            self.optimizer.step()
         self.global_step += 1
+        self._poll_nonfinite()
         return self._global_loss(model, loss)
 
     def _global_loss(self, model, loss):
@@ -151,6 +240,7 @@ class Trainer:
 
     @torch.no_grad()
     def evaluate(self, model, loader, split="val"):
+        self._poll_nonfinite(now=True)
         model.eval()
         tot, n = 0.0, 0
         for i, batch in enumerate(loader):
@@ -186,6 +276,7 @@ class Trainer:
                 self.save_checkpoint(model, os.path.join(ckpt_dir, "last.ckpt"))
             if max_steps is not None and self.global_step >= max_steps:
                 break
+        self._poll_nonfinite(now=True)
         return history
 
     def _log(self, rec):
@@ -195,6 +286,7 @@ class Trainer:
 
     # ------------------------------------------------------------------ checkpoints (reference layout + resume state)
     def save_checkpoint(self, model, path):
+        self._poll_nonfinite(now=True)
         os.makedirs(os.path.dirname(path) or ".", exist_ok=True)
         ckpt = model.checkpoint()
         if self.flat:        # the reference layout holds fp32 weights: write the masters, not the bf16 shadows
@@ -205,6 +297,10 @@ class Trainer:
         ckpt["optimizer_states"] = [self.optimizer.state_dict()]
         ckpt["global_step"] = self.global_step
         ckpt["epoch"] = model.current_epoch
+        if self._record is not None:         # optimizer `step` holds the applied steps; the skip counters travel here
+            r = self._record.tolist()
+            ckpt["nonfinite"] = {"applied": r[NF.APPLIED], "skipped": r[NF.SKIPPED], "consecutive": r[NF.CONSECUTIVE],
+                                 "longest": r[NF.LONGEST], "calls": self.optimizer.calls if self.flat else self.global_step}
         torch.save(ckpt, path)
 
     def resume(self, model, path):
@@ -218,6 +314,28 @@ class Trainer:
             self.optimizer.load_state_dict(ckpt["optimizer_states"][0])
         self.global_step = ckpt.get("global_step", 0)
         model.current_epoch = ckpt.get("epoch", 0)
+        nf = ckpt.get("nonfinite")
+        if nf is not None and self._record is not None:
+            r = self._record
+            for k, slot in (("skipped", NF.SKIPPED), ("consecutive", NF.CONSECUTIVE), ("longest", NF.LONGEST)):
+                r[slot] = int(nf[k])
+            if self.flat:
+                self.optimizer.calls = max(self.optimizer.calls, int(nf["calls"]))
+            else:
+                r[NF.APPLIED] = int(nf["applied"])
+            self.monitor.seen_skipped = int(nf["skipped"])
+
+
+class _Snapshot:
+    """a record copy in flight: wait() blocks on its event (never queried: gloria/nonfinite.py)"""
+
+    def __init__(self, event, buf):
+        self.event, self.buf = event, buf
+
+    def wait(self):
+        if self.event is not None:
+            self.event.synchronize()
+        return self.buf.tolist()
 
 
 class _Null:

@@ -516,6 +516,45 @@ int glr_adam_step(float* master, float* exp_avg, float* exp_avg_sq, const void* 
                   long long n, float lr, float beta1, float beta2, float eps, float weight_decay, int step,
                   const float* clip, void* stream);
 
+/* Guarded step (GradScaler's skip, decided on the device): the same three stages, and a step whose gradients hold ANY
+ * inf / NaN element is skipped - nothing is written to the masters, moments or shadows.
+ *   glr_sumsq_partial_g, glr_sumsq_mt_g   the partials of the plain forms, bitwise, and per partial b
+ *                       nonfinite[2 b] = its non-finite element count, nonfinite[2 b + 1] = the smallest element offset
+ *                       among them (-1: none): an offset into x (flat form) or into the chunk (pointer-table form)
+ *   glr_step_guard      out[] exactly as glr_clip_coef, and the step's record in record[GLR_GUARD_WORDS] (int64):
+ *                       finite -> APPLIED += 1, CONSECUTIVE = 0, SKIP = 0; otherwise SKIPPED += 1, CONSECUTIVE += 1,
+ *                       SKIP = 1, LAST_CALL = call_index, LAST_COUNT = non-finite elements of the step, LAST_PARTIAL /
+ *                       LAST_OFFSET = partial index and offset of its first one, LONGEST = longest CONSECUTIVE run.
+ *                       Finite elements whose norm overflows are NOT skipped (coefficient 0, as glr_clip_coef).
+ *   glr_adam_step_g, glr_adam_step_mt_g   return at once when record[SKIP] != 0; else the plain forms' arithmetic with
+ *                       bc1 = bias_table[2 (t - 1)], bc2_sqrt = bias_table[2 (t - 1) + 1], t = record[APPLIED]
+ *                       (device memory, t clamped to [1, bias_capacity])
+ *   glr_adam_bias_table HOST memory, no GPU: out[2 (t - 1)] = 1 - beta1^t, out[2 (t - 1) + 1] = sqrt(1 - beta2^t) for
+ *                       t = 1 .. capacity, by the float expressions the plain launch wrappers evaluate per call. */
+#define GLR_GUARD_APPLIED 0
+#define GLR_GUARD_SKIPPED 1
+#define GLR_GUARD_CONSECUTIVE 2
+#define GLR_GUARD_SKIP 3
+#define GLR_GUARD_LAST_CALL 4
+#define GLR_GUARD_LAST_COUNT 5
+#define GLR_GUARD_LAST_PARTIAL 6
+#define GLR_GUARD_LAST_OFFSET 7
+#define GLR_GUARD_LONGEST 8
+#define GLR_GUARD_WORDS 16
+int glr_sumsq_partial_g(const void* x, int dtype, long long n, float* partial, int64_t* nonfinite, void* stream);
+int glr_sumsq_mt_g(const void* chunk_table, int n_chunks, const uint64_t* grad_ptrs, int dtype, float* partial,
+                   int64_t* nonfinite, void* stream);
+int glr_step_guard(const float* partial, const int64_t* nonfinite, int n_partial, float max_norm, float* out,
+                   int64_t* record, long long call_index, void* stream);
+int glr_adam_step_g(float* master, float* exp_avg, float* exp_avg_sq, const void* grad, int grad_dtype, void* shadow_bf16,
+                    long long n, float lr, float beta1, float beta2, float eps, float weight_decay, const float* bias_table,
+                    int bias_capacity, const int64_t* record, const float* clip, void* stream);
+int glr_adam_step_mt_g(const void* chunk_table, int n_chunks, const uint64_t* grad_ptrs, int grad_dtype, float* master,
+                       float* exp_avg, float* exp_avg_sq, void* shadow_bf16, float lr, float beta1, float beta2, float eps,
+                       float weight_decay, const float* bias_table, int bias_capacity, const int64_t* record,
+                       const float* clip, void* stream);
+int glr_adam_bias_table(float beta1, float beta2, int capacity, float* out);
+
 #ifdef __cplusplus
 }
 #endif
