@@ -1,6 +1,8 @@
 // K1 launch parameters and constants shared by the local-attention kernels (glr_local_attn.hip: single-tile and pair
 // kernels, forward and backward; glr_local_attn_t1.hip: the 4-wave single-tile forward).
 #pragma once
+#include <cstdlib>
+
 #include "glr_common.h"
 
 constexpr int TW = GLR_TILE_WORDS;  // 64 word slots per tile
@@ -35,7 +37,7 @@ struct LaParams {
   int strip;
   int pair_only, img_offset;
   int img_block;                // pair kernel: images per L2 group (block -> (image, item) mapping)
-  const int* pair_desc;         // [n_pair][64] sentences + row flags of every forward pair (glr_plan_pair_desc)
+  const int* pair_desc;         // [n_pair][64] sentences + row flags of every forward pair (glr_plan_build)
   unsigned* a1buf;              // optional [B_img][n_pair][8 waves][2][3][8][64] fp16 pairs of a1 in the pair kernels' own
                                 // register order: written by the forward, read by the backward instead of its score stream
   int a1_items, a1_base;        // pairs per image in a1buf (all pairs of the plan) and the index of this launch's first pair
@@ -68,7 +70,20 @@ __host__ __device__ __forceinline__ constexpr int glr_ktile_off(int row, int slo
   return (row >> 5) * 2048 + slot * 512 + (row & 31) * 16;
 }
 
-constexpr int PW_MAXSEG = 8;    // sentences per pair (planner: max_pair_seg); the spanning sentence of a long pair uses rows 0 / 1
+constexpr int PW_MAXSEG = GLR_MAX_PAIR_SEG;   // sentences per pair (the planner's limit); the spanning sentence of a long pair uses rows 0 / 1
+
+// Grid of a launch over pairs: 8 XCDs x images per XCD, rounded up to a multiple of the L2 group size p.img_block
+// (set here: GLR_K1_IMG_BLOCK, default 4), x p.n_items pairs x wgs_per_item workgroups.  The diagnostic ablate build
+// also reads its phase mask (GLR_K1_DBG) here.
+inline int glr_k1_pair_grid(LaParams& p, int wgs_per_item) {
+  static const int env_ib = [] { const char* e = getenv("GLR_K1_IMG_BLOCK"); return e ? atoi(e) : 0; }();
+  p.img_block = env_ib > 0 ? env_ib : 4;
+  const int per_xcd = ((p.B_img + 7) / 8 + p.img_block - 1) / p.img_block * p.img_block;
+#ifdef GLR_ABLATE
+  { const char* e = getenv("GLR_K1_DBG"); p.dbg = e ? atoi(e) : 0; }
+#endif
+  return per_xcd * 8 * p.n_items * wgs_per_item;
+}
 
 // forward of the ordinary (two whole 64-slot tiles, <= 8 sentences) pairs, one 4-wave workgroup per tile
 // (glr_local_attn_t1.hip); p.item_tile / p.pair_desc / p.n_items describe those pairs, p.a1_base their position in a1buf

@@ -1255,10 +1255,10 @@ __global__ void __launch_bounds__(NTHR) k_local_attn_pw(LaParams p) {
 // Backward for a PAIR of tiles, wave-owned words: the forward pair kernel's decomposition (same descriptor, same
 // streams, same lane -> (word row, region) mapping) applied to autograd through gloria_loss.py:19-63, 150-164.
 //   set-up  per-word scalars (alpha, beta, kappa, 1/Z: float4 per slot) from dsim and the forward's statistics;
-//           the lse rows of the pair's sentences -> LDS (log2 units).  Their global loads are issued before the
-//           score stream and consumed after it.
-//   P1      acc = s = T V^T                                  (stream of vt[b], both tiles)
-//   P2      a1 = exp2(s log2e - lse), a2 = exp2(temp1 log2e a1) / Z; image = bf16(beta a2); acc = -alpha s;
+//           the lse rows of the pair's sentences -> LDS (log2 units); a1 of the forward pair kernels
+//           (LaParams::a1buf, fp16 pairs in this kernel's own register order) -> registers.  There is no score
+//           stream: the score itself, needed for -alpha s, is s = lse + log(a1).
+//   P2      a2 = exp2(temp1 log2e a1) / Z; image = bf16(beta a2); acc = -alpha s;
 //           a1 stays in registers as fp16 pairs (48 registers; fp32 copies do not fit beside 96 accumulators)
 //   P3      acc += image . G^T = beta u - alpha s = -da2      (stream of gram[b])
 //   A       da1 = temp1 a2 (da2 - kappa); run sums of a1 da1 per (sentence, region) -> one-writer half tables
@@ -1267,15 +1267,12 @@ __global__ void __launch_bounds__(NTHR) k_local_attn_pw(LaParams p) {
 //           X = acc - a1 rho -> image -> xout
 // Optional third output baout = the P3 operand image beta a2 (saves the caller an elementwise pass in front of the
 // P = (beta a2)^T a2 GEMM).  Empty word slots have zero scalars: their rows of every output are exact zeros.
-// A1IN: the forward pair kernel handed over a1 (LaParams::a1buf, fp16 pairs in this kernel's own register order): no
-// score stream; the score itself, needed for -alpha s, is lse + log(a1).
-// AUX (with A1IN only): the extra gradient inputs `damean` (word-mean attention rows: regularisers) and `dattn` (diagonal
+// AUX: the extra gradient inputs `damean` (word-mean attention rows: regularisers) and `dattn` (diagonal
 // attention maps: attention supervision), g[w, r] = damean[b, sentence(w), r] / n_words (+ dattn[w, r] on the diagonal
 // pair): da2 gains g, i.e. the accumulator starts at -(alpha s + g), and kappa_w gains sum_r a2[w, r] g[w, r].  The
-// damean rows of the pair's sentences are parked in LDS beside the lse rows (the P1 ring is not used with A1IN).
-template <typename O, bool A1IN, bool AUX = false>
+// damean rows of the pair's sentences are parked in LDS beside the lse rows.
+template <typename O, bool AUX>
 __global__ void __launch_bounds__(NTHR) k_local_attn_pw_bwd(LaParams p) {
-  static_assert(A1IN || !AUX, "the extra gradient inputs ride on the a1 hand-over variant");
   constexpr int ESZ = O::ESZ, CB = CHB;
   constexpr int SP = GLR_MAX_SPAD;
   constexpr int NRB = SP / 32;
@@ -1283,7 +1280,7 @@ __global__ void __launch_bounds__(NTHR) k_local_attn_pw_bwd(LaParams p) {
   constexpr int IMG = TW * IMP;
   constexpr int PPR = SP * ESZ / 16;                              // 16-byte pieces per output row
   constexpr float LOG2E = 1.4426950408889634f, LN2 = 0.6931471805599453f;
-  constexpr int LT_OFF = NBUF * (2 * TW + SP) * CB;               // first byte past the P1 ring
+  constexpr int LT_OFF = NBUF * (2 * TW + SP) * CB;               // lse table: past the images and the tables at off_img
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
 
   const int tid = threadIdx.x;
@@ -1299,9 +1296,8 @@ __global__ void __launch_bounds__(NTHR) k_local_attn_pw_bwd(LaParams p) {
   if (b >= p.B_img) return;
   GLR_STAMP2(0);
   const int tile0 = p.item_tile[rem / ib];
-  const int D = p.D;
   unsigned a1k0[3][8], a1k1[3][8];                                // a1 as fp16 pairs (rows q, q + 1)
-  if constexpr (A1IN) {
+  {
     // 48 coalesced dword loads per lane, in flight behind the whole set-up
     const unsigned* a1in = p.a1buf + (((size_t)b * p.a1_items + p.a1_base + rem / ib) * 8 + wave) * (2 * 3 * 8 * 64) + lane;
 #pragma unroll
@@ -1310,7 +1306,6 @@ __global__ void __launch_bounds__(NTHR) k_local_attn_pw_bwd(LaParams p) {
       for (int i = 0; i < 8; ++i) { a1k0[j][i] = a1in[(j * 8 + i) * 64]; a1k1[j][i] = a1in[((3 + j) * 8 + i) * 64]; }
   }
 
-  unsigned char* ring = smem;
   unsigned char* img0 = smem;
   float* rh = reinterpret_cast<float*>(smem + p.off_img);        // [2][PW_MAXSEG][SP] run sums of a1 da1 (after P3)
   constexpr int HT = PW_MAXSEG * SP;
@@ -1326,8 +1321,7 @@ __global__ void __launch_bounds__(NTHR) k_local_attn_pw_bwd(LaParams p) {
   [[maybe_unused]] float* kred = zero + SP;                      // AUX: [8][2 * TW] partial sums of a2 g per word
   [[maybe_unused]] float* gt = reinterpret_cast<float*>(smem + p.off_img);   // AUX: [PW_MAXSEG][SP] damean / n (P2 only)
 
-  const size_t rowbytes1 = (size_t)D * ESZ, rowbytes2 = (size_t)SP * ESZ;
-  const unsigned char* vt_b = p.vt + (size_t)b * SP * rowbytes1;
+  const size_t rowbytes2 = (size_t)SP * ESZ;
   const unsigned char* gram_b = p.gram + (size_t)b * SP * rowbytes2;
 
   int* dsc = misc + 16;
@@ -1355,7 +1349,7 @@ __global__ void __launch_bounds__(NTHR) k_local_attn_pw_bwd(LaParams p) {
     if (AUX && sent == p.img_offset + b) { misc[1] = w0; misc[2] = n; }
   }
   __syncthreads();
-  // second round trip, issued here and consumed behind the score stream: dsim / sim of the slot's sentence, and the
+  // second round trip: dsim / sim of the slot's sentence, and the
   // lse rows of the pair's sentences (6 coalesced values per thread)
   float gsim = 0.f, vsim = 0.f;
   int sgw = -1;
@@ -1407,17 +1401,12 @@ __global__ void __launch_bounds__(NTHR) k_local_attn_pw_bwd(LaParams p) {
   }
   __syncthreads();
 
-  // ================= P1 (both tiles, one stream of vt[b]) =================
   GLR_STAMP2(1);
   f32x16 acc0[3], acc1[3];
 #pragma unroll
   for (int j = 0; j < 3; ++j)
 #pragma unroll
     for (int q = 0; q < 16; ++q) { acc0[j][q] = 0.f; acc1[j][q] = 0.f; }
-  if constexpr (!A1IN)
-  if (!GLR_SKIP(1))
-  stream_gemm<O, false, 2>(acc0, acc1, t * TW, 32 * CB, ring, (2 * TW + SP) * CB, p.tp + (size_t)tile0 * TW * rowbytes1,
-                           rowbytes1, vt_b, rowbytes1, SP, (int)(rowbytes1 / CB), nullptr, 0, wave, lane, 0, wg, NRB, TW);
   GLR_STAMP2(2);
 
   const int* fl = dsc + 32 + 8 * t;
@@ -1450,7 +1439,6 @@ __global__ void __launch_bounds__(NTHR) k_local_attn_pw_bwd(LaParams p) {
     for (int blk = 0; blk < 2; ++blk) {
       f32x16(&acc)[3] = blk == 0 ? acc0 : acc1;
       unsigned(&a1k)[3][8] = blk == 0 ? a1k0 : a1k1;
-      [[maybe_unused]] float a1e[3] = {0.f, 0.f, 0.f};
       [[maybe_unused]] float zq[4];                // reduced across lanes every four rows (interleaved DPP chains)
 #pragma unroll
       for (int q = 0; q < 16; ++q) {
@@ -1487,24 +1475,11 @@ __global__ void __launch_bounds__(NTHR) k_local_attn_pw_bwd(LaParams p) {
         [[maybe_unused]] float zacc = 0.f;
 #pragma unroll
         for (int j = 0; j < 3; ++j) {
-          float a1, sc;
-          if constexpr (A1IN) {
-            const h2 hp = __builtin_bit_cast(h2, a1k[j][q >> 1]);
-            a1 = (float)((q & 1) ? hp.y : hp.x);                      // <= 1: the forward clamps what it hands over
-            sc = (lc[j] + __builtin_amdgcn_logf(fmaxf(a1, 5.9604645e-8f))) * LN2;     // s = lse + log a1
-          } else {
-            float x = __builtin_fmaf(acc[j][q], LOG2E, -lc[j]);
-            asm("v_min_f32 %0, 0, %1" : "=v"(x) : "v"(x));        // empty slots: stale lse, keep a1 finite
-            a1 = __builtin_amdgcn_exp2f(x);
-            sc = acc[j][q];
-          }
+          const h2 hp = __builtin_bit_cast(h2, a1k[j][q >> 1]);
+          const float a1 = (float)((q & 1) ? hp.y : hp.x);            // <= 1: the forward clamps what it hands over
+          const float sc = (lc[j] + __builtin_amdgcn_logf(fmaxf(a1, 5.9604645e-8f))) * LN2;     // s = lse + log a1
           const float a2 = __builtin_amdgcn_exp2f(t1l * a1) * w.x;
           O::from_f32(imgw + row * IMP + 128 * j * ESZ, w.y * a2);
-          if constexpr (!A1IN) {
-            // (volatile: the compiler otherwise sinks the conversion to its use behind P3 and keeps - spills - 96 fp32 values)
-            if (q & 1) asm volatile("v_cvt_pkrtz_f16_f32 %0, %1, %2" : "=v"(a1k[j][q >> 1]) : "v"(a1e[j]), "v"(a1));
-            else a1e[j] = a1;
-          }
           if constexpr (AUX) {
             acc[j][q] = __builtin_fmaf(-w.z, sc, -ge[j]);       // da2 = (alpha s - beta u) + g
             zacc = __builtin_fmaf(a2, ge[j], zacc);             // kappa gains sum_r a2 g (softmax-over-regions backward)
@@ -1554,13 +1529,11 @@ __global__ void __launch_bounds__(NTHR) k_local_attn_pw_bwd(LaParams p) {
   }
 
   // ================= A: da1, run sums of a1 da1, a2 image =================
-  if constexpr (A1IN) {
-    // (opaque copies: the compiler otherwise keeps P2's unpacked fp32 a1 alive - spilled - for this pass)
+  // (opaque copies: the compiler otherwise keeps P2's unpacked fp32 a1 alive - spilled - for this pass)
 #pragma unroll
-    for (int j = 0; j < 3; ++j)
+  for (int j = 0; j < 3; ++j)
 #pragma unroll
-      for (int i = 0; i < 8; ++i) { asm volatile("" : "+v"(a1k0[j][i])); asm volatile("" : "+v"(a1k1[j][i])); }
-  }
+    for (int i = 0; i < 8; ++i) { asm volatile("" : "+v"(a1k0[j][i])); asm volatile("" : "+v"(a1k1[j][i])); }
   GLR_STAMP2(5);
   const int nrow = long_pair ? 2 : NS;
   {
@@ -1733,16 +1706,9 @@ int launch_pair(LaParams& p, int op_dtype, void* stream) {
   if (p.S_pad != GLR_MAX_SPAD) return GLR_EINVAL;   // the pair kernels are built for the 384-region shape only
   const int lds = carve_pair(p, op_dtype, p.S_pad);
   if (lds > 160 * 1024) return GLR_EINVAL;
-  // images per XCD rounded up to a multiple of the L2 group size
-  static const int env_ib = [] { const char* e = getenv("GLR_K1_IMG_BLOCK"); return e ? atoi(e) : 0; }();
-  p.img_block = env_ib > 0 ? env_ib : 4;
-  const int per_xcd = ((p.B_img + 7) / 8 + p.img_block - 1) / p.img_block * p.img_block;
-  const int grid = per_xcd * 8 * p.n_items;
   // the pair kernel needs the planner's row flags and a spare padded region for the ones row of the Gram operand
   if (p.pair_desc == nullptr || p.S_eff >= p.S_pad) return GLR_EINVAL;
-#ifdef GLR_ABLATE
-  { const char* e = getenv("GLR_K1_DBG"); p.dbg = e ? atoi(e) : 0; }
-#endif
+  const int grid = glr_k1_pair_grid(p, 1);
   static GlrLdsAttr la_pw;
   if (glr_ensure_lds(la_pw, (const void*)k_local_attn_pw<OpBF16>, lds) != GLR_OK) return GLR_ELAUNCH;
   hipLaunchKernelGGL((k_local_attn_pw<OpBF16>), dim3(grid), dim3(NTHR), lds, (hipStream_t)stream, p);
@@ -1752,49 +1718,51 @@ int launch_pair(LaParams& p, int op_dtype, void* stream) {
 
 int launch_pair_bwd(LaParams& p, int op_dtype, void* stream) {
   if (op_dtype != GLR_BF16 || p.S_pad != GLR_MAX_SPAD) return GLR_EINVAL;
-  const bool aux = p.damean != nullptr || p.dattn != nullptr;
-  if (aux && p.a1buf == nullptr) return GLR_EINVAL;   // without the a1 hand-over the extra gradient inputs take the single-tile kernel
+  if (p.a1buf == nullptr) return GLR_EINVAL;        // the scores come from the a1 the forward handed over
   const int lds = carve_pair(p, op_dtype, p.S_pad);
-  // lse table behind the P1 ring, in front of the small area
+  // the kernel's lse table (LT_OFF) lies in front of the small area
   if (lds > 160 * 1024 || NBUF * (2 * TW + p.S_pad) * CHB + PW_MAXSEG * p.S_pad * 4 > p.off_small) return GLR_EINVAL;
-  static const int env_ib = [] { const char* e = getenv("GLR_K1_IMG_BLOCK"); return e ? atoi(e) : 0; }();
-  p.img_block = env_ib > 0 ? env_ib : 4;
-  const int per_xcd = ((p.B_img + 7) / 8 + p.img_block - 1) / p.img_block * p.img_block;
-  const int grid = per_xcd * 8 * p.n_items;
   if (p.pair_desc == nullptr || p.S_eff >= p.S_pad) return GLR_EINVAL;
-#ifdef GLR_ABLATE
-  { const char* e = getenv("GLR_K1_DBG"); p.dbg = e ? atoi(e) : 0; }
-#endif
-  if (aux) {
+  const int grid = glr_k1_pair_grid(p, 1);
+  if (p.damean != nullptr || p.dattn != nullptr) {
     static GlrLdsAttr la_b2;
-    if (glr_ensure_lds(la_b2, (const void*)k_local_attn_pw_bwd<OpBF16, true, true>, lds) != GLR_OK) return GLR_ELAUNCH;
-    hipLaunchKernelGGL((k_local_attn_pw_bwd<OpBF16, true, true>), dim3(grid), dim3(NTHR), lds, (hipStream_t)stream, p);
-  } else if (p.a1buf != nullptr) {
-    static GlrLdsAttr la_b1;
-    if (glr_ensure_lds(la_b1, (const void*)k_local_attn_pw_bwd<OpBF16, true>, lds) != GLR_OK) return GLR_ELAUNCH;
+    if (glr_ensure_lds(la_b2, (const void*)k_local_attn_pw_bwd<OpBF16, true>, lds) != GLR_OK) return GLR_ELAUNCH;
     hipLaunchKernelGGL((k_local_attn_pw_bwd<OpBF16, true>), dim3(grid), dim3(NTHR), lds, (hipStream_t)stream, p);
   } else {
-    static GlrLdsAttr la_b0;
-    if (glr_ensure_lds(la_b0, (const void*)k_local_attn_pw_bwd<OpBF16, false>, lds) != GLR_OK) return GLR_ELAUNCH;
+    static GlrLdsAttr la_b1;
+    if (glr_ensure_lds(la_b1, (const void*)k_local_attn_pw_bwd<OpBF16, false>, lds) != GLR_OK) return GLR_ELAUNCH;
     hipLaunchKernelGGL((k_local_attn_pw_bwd<OpBF16, false>), dim3(grid), dim3(NTHR), lds, (hipStream_t)stream, p);
   }
   GLR_CHECK_LAUNCH();
   return GLR_OK;
 }
 
-int fill_common(LaParams& p, const void* vt, const void* gram, const void* tp, const float* tnorm,
-                const int32_t* sent_slot0, const int32_t* cap_lens, const int32_t* tile_first, const int32_t* order,
-                const int32_t* tile_nsub, int n_tiles, int n_sent, int B_img, int D, int S_eff, float temp1,
-                float temp2, float temp3, int agg, float eps, int op_dtype) {
-  if (!vt || !gram || !tp || !tnorm || !sent_slot0 || !cap_lens || !tile_first || !order || !tile_nsub) return GLR_EINVAL;
+// Everything the two entry points share: argument checks, the plan header (host) -> counts and device pointers.
+int fill_common(LaParams& p, const void* vt, const void* gram, const void* tp, const float* tnorm, const int32_t* plan,
+                const int32_t* plan_dev, int B_img, int D, int S_eff, float temp1, float temp2, float temp3, int agg,
+                float eps, int op_dtype) {
+  if (!vt || !gram || !tp || !tnorm || !plan || !plan_dev) return GLR_EINVAL;
   if (op_dtype != GLR_F32 && op_dtype != GLR_BF16) return GLR_EDTYPE;
+  const int n_sent = plan[GLR_PLAN_N_SENT], n_tiles = plan[GLR_PLAN_N_TILES], n_ints = plan[GLR_PLAN_N_INTS];
+  const int n_pair = plan[GLR_PLAN_N_PAIR];
   if (n_tiles <= 0 || n_sent <= 0 || B_img <= 0 || S_eff <= 0 || D <= 0 || D % 64 != 0) return GLR_EINVAL;
+  if (plan[GLR_PLAN_N_ORDER] < 0 || plan[GLR_PLAN_N_SINGLE] < 0 || n_pair < 0 || plan[GLR_PLAN_N_LONG_PAIR] < 0 ||
+      plan[GLR_PLAN_N_LONG_PAIR] > n_pair || plan[GLR_PLAN_CAPACITY] != glr_tile_capacity(op_dtype))
+    return GLR_EINVAL;
+  const int len[8] = {n_sent, n_sent, n_tiles + 1, plan[GLR_PLAN_N_ORDER], n_tiles, plan[GLR_PLAN_N_SINGLE], n_pair, 64 * n_pair};
+  for (int a = 0; a < 8; ++a) {
+    const int off = plan[GLR_PLAN_OFF_CAP_LENS + a];
+    if (off < GLR_PLAN_HEADER || (long long)off + len[a] > n_ints) return GLR_EINVAL;
+  }
   const int S_pad = glr_region_pad(S_eff);
   if (S_pad > GLR_MAX_SPAD) return GLR_EINVAL;
   if (agg < 0 || agg > 2) return GLR_EINVAL;
   p.vt = (const unsigned char*)vt; p.gram = (const unsigned char*)gram; p.tp = (const unsigned char*)tp;
-  p.tnorm = tnorm; p.sent_slot0 = sent_slot0; p.cap_lens = cap_lens; p.tile_first = tile_first; p.order = order;
-  p.tile_nsub = tile_nsub; p.item_tile = nullptr; p.n_items = 0; p.amean = nullptr; p.damean = nullptr; p.dattn = nullptr; p.pair_desc = nullptr; p.a1buf = nullptr; p.a1_items = 0; p.a1_base = 0; p.n_tiles = n_tiles; p.n_sent = n_sent;
+  p.tnorm = tnorm;
+  p.cap_lens = plan_dev + plan[GLR_PLAN_OFF_CAP_LENS]; p.sent_slot0 = plan_dev + plan[GLR_PLAN_OFF_SENT_SLOT0];
+  p.tile_first = plan_dev + plan[GLR_PLAN_OFF_TILE_FIRST]; p.order = plan_dev + plan[GLR_PLAN_OFF_ORDER];
+  p.tile_nsub = plan_dev + plan[GLR_PLAN_OFF_TILE_NSUB];
+  p.item_tile = nullptr; p.n_items = 0; p.amean = nullptr; p.damean = nullptr; p.dattn = nullptr; p.pair_desc = nullptr; p.a1buf = nullptr; p.a1_items = 0; p.a1_base = 0; p.n_tiles = n_tiles; p.n_sent = n_sent;
   p.n_slots = n_tiles * TW; p.B_img = B_img;
   p.D = D; p.S_eff = S_eff; p.S_pad = S_pad; p.temp1 = temp1; p.temp2 = temp2; p.temp3 = temp3; p.agg = agg;
   p.eps = eps;
@@ -1812,32 +1780,28 @@ int fill_common(LaParams& p, const void* vt, const void* gram, const void* tp, c
 }  // namespace
 
 extern "C" int glr_local_attn_fwd(const void* vt, const void* gram, const void* tp, const float* tnorm,
-                                  const int32_t* sent_slot0, const int32_t* cap_lens,
-                                  const int32_t* tile_first, const int32_t* order, const int32_t* tile_nsub,
-                                  const int32_t* single_tile, int n_single, const int32_t* pair_tile, int n_pair,
-                                  int n_long_pair, const int32_t* pair_desc,
-                                  int n_tiles, int n_sent, int B_img, int D, int S_eff, float temp1, float temp2,
-                                  float temp3, int agg, float eps, float* sim, int ld_sim, float* lse, float* wstat,
-                                  float* attn, const int64_t* attn_off, int strip, int pair_only, int img_offset,
-                                  float* amean, void* a1buf, int op_dtype, void* stream) {
+                                  const int32_t* plan, const int32_t* plan_dev, int B_img, int D, int S_eff, float temp1,
+                                  float temp2, float temp3, int agg, float eps, float* sim, int ld_sim, float* lse,
+                                  float* wstat, float* attn, const int64_t* attn_off, int strip, int pair_only,
+                                  int img_offset, float* amean, void* a1buf, int op_dtype, void* stream) {
   LaParams p;
-  int rc = fill_common(p, vt, gram, tp, tnorm, sent_slot0, cap_lens, tile_first, order, tile_nsub, n_tiles,
-                       n_sent, B_img, D, S_eff, temp1, temp2, temp3, agg, eps, op_dtype);
+  int rc = fill_common(p, vt, gram, tp, tnorm, plan, plan_dev, B_img, D, S_eff, temp1, temp2, temp3, agg, eps, op_dtype);
   if (rc != GLR_OK) return rc;
+  const int n_single = plan[GLR_PLAN_N_SINGLE], n_pair = plan[GLR_PLAN_N_PAIR], n_long_pair = plan[GLR_PLAN_N_LONG_PAIR];
+  const int32_t* pair_tile = plan_dev + plan[GLR_PLAN_OFF_PAIR_TILE];
+  const int32_t* pair_desc = plan_dev + plan[GLR_PLAN_OFF_PAIR_DESC];
   if (!sim || (attn && !attn_off)) return GLR_EINVAL;
-  if (n_single < 0 || n_pair < 0 || (n_single > 0 && !single_tile) || (n_pair > 0 && !pair_tile)) return GLR_EINVAL;
-  if (pair_only && img_offset + B_img > n_sent) return GLR_EINVAL;
+  if (pair_only && img_offset + B_img > p.n_sent) return GLR_EINVAL;
   if (!pair_only && n_single + n_pair == 0) return GLR_EINVAL;
   if (amean && pair_only) return GLR_EINVAL;
   p.sim = sim; p.ld_sim = ld_sim; p.lse = lse; p.wstat = wstat; p.attn = attn; p.amean = amean;
   p.attn_off = (const long long*)attn_off; p.strip = strip; p.pair_only = pair_only; p.img_offset = img_offset;
   if (pair_only || n_single > 0) {
-    p.item_tile = single_tile; p.n_items = n_single;
+    p.item_tile = plan_dev + plan[GLR_PLAN_OFF_SINGLE_TILE]; p.n_items = n_single;
     rc = launch<false>(p, op_dtype, stream);
     if (rc != GLR_OK) return rc;
   }
   if (!pair_only && n_pair > 0) {
-    if (n_long_pair < 0 || n_long_pair > n_pair) return GLR_EINVAL;
     // The pairs of one 65..128-word sentence (a prefix of the pair list: the planner puts multi-tile sentences first) run
     // the 8-wave pair kernel; the ordinary pairs (two whole tiles) run one 4-wave workgroup per tile, two per CU
     // (glr_local_attn_t1.hip).  GLR_K1_T1=0 sends every pair to the pair kernel (A/B switch of tools/ and tests).
@@ -1858,37 +1822,34 @@ extern "C" int glr_local_attn_fwd(const void* vt, const void* gram, const void* 
 }
 
 extern "C" int glr_local_attn_bwd(const void* vt, const void* gram, const void* tp, const float* tnorm,
-                                  const int32_t* sent_slot0, const int32_t* cap_lens,
-                                  const int32_t* tile_first, const int32_t* order, const int32_t* tile_nsub,
-                                  const int32_t* single_tile, int n_single, const int32_t* pair_tile, int n_pair,
-                                  const int32_t* pair_desc, int n_tiles, int n_sent, int B_img, int D,
-                                  int S_eff, float temp1, float temp2, float temp3, int agg, float eps,
-                                  const float* sim, const float* dsim, int ld_sim, const float* lse,
-                                  const float* wstat, const float* damean, const float* dattn,
-                                  const int64_t* attn_off, int strip, int img_offset, void* xout, void* aout,
-                                  void* baout, float* gamma, float* beta, const void* a1buf, int op_dtype, void* stream) {
+                                  const int32_t* plan, const int32_t* plan_dev, int B_img, int D, int S_eff, float temp1,
+                                  float temp2, float temp3, int agg, float eps, const float* sim, const float* dsim,
+                                  int ld_sim, const float* lse, const float* wstat, const float* damean,
+                                  const float* dattn, const int64_t* attn_off, int strip, int img_offset, void* xout,
+                                  void* aout, void* baout, float* gamma, float* beta, const void* a1buf, int op_dtype,
+                                  void* stream) {
   LaParams p;
-  int rc = fill_common(p, vt, gram, tp, tnorm, sent_slot0, cap_lens, tile_first, order, tile_nsub, n_tiles,
-                       n_sent, B_img, D, S_eff, temp1, temp2, temp3, agg, eps, op_dtype);
+  int rc = fill_common(p, vt, gram, tp, tnorm, plan, plan_dev, B_img, D, S_eff, temp1, temp2, temp3, agg, eps, op_dtype);
   if (rc != GLR_OK) return rc;
+  const int n_single = plan[GLR_PLAN_N_SINGLE], n_pair = plan[GLR_PLAN_N_PAIR];
   if (!sim || !dsim || !lse || !wstat || !xout || !aout || !gamma || !beta) return GLR_EINVAL;
-  if (n_single < 0 || n_pair < 0 || n_single + n_pair == 0 || (n_single > 0 && !single_tile) || (n_pair > 0 && (!pair_tile || !pair_desc)))
-    return GLR_EINVAL;
+  if (n_single + n_pair == 0) return GLR_EINVAL;
   if (agg == GLR_AGG_MAX) return GLR_EINVAL;      // max aggregation is inference-only (gloria_model.py:199)
   p.sim = const_cast<float*>(sim); p.dsim = dsim; p.ld_sim = ld_sim; p.lse = const_cast<float*>(lse);
   p.wstat = const_cast<float*>(wstat); p.xout = (unsigned char*)xout; p.aout = (unsigned char*)aout;
   p.baout = (unsigned char*)baout;
   if (dattn && !attn_off) return GLR_EINVAL;
-  if (img_offset < 0 || img_offset + B_img > n_sent) return GLR_EINVAL;
+  if (img_offset < 0 || img_offset + B_img > p.n_sent) return GLR_EINVAL;
   p.gamma = gamma; p.beta = beta; p.damean = damean;
   p.dattn = dattn; p.attn_off = (const long long*)attn_off; p.strip = strip; p.img_offset = img_offset;
   if (n_single > 0) {
-    p.item_tile = single_tile; p.n_items = n_single;
+    p.item_tile = plan_dev + plan[GLR_PLAN_OFF_SINGLE_TILE]; p.n_items = n_single;
     rc = launch<true>(p, op_dtype, stream);
     if (rc != GLR_OK) return rc;
   }
   if (n_pair > 0) {
-    p.item_tile = pair_tile; p.n_items = n_pair; p.pair_desc = pair_desc; p.a1buf = (unsigned*)const_cast<void*>(a1buf);
+    p.item_tile = plan_dev + plan[GLR_PLAN_OFF_PAIR_TILE]; p.n_items = n_pair;
+    p.pair_desc = plan_dev + plan[GLR_PLAN_OFF_PAIR_DESC]; p.a1buf = (unsigned*)const_cast<void*>(a1buf);
     p.a1_items = n_pair; p.a1_base = 0;
     rc = launch_pair_bwd(p, op_dtype, stream);
   }

@@ -581,13 +581,7 @@ int glr_k1_launch_tiles(LaParams& p, int op_dtype, void* stream) {
   if (op_dtype != GLR_BF16 || p.S_pad != SP) return GLR_EINVAL;
   if (p.pair_desc == nullptr || p.S_eff >= p.S_pad || p.n_items <= 0) return GLR_EINVAL;
   if (p.D % 128 != 0 || p.D < 256) return GLR_EINVAL;   // the score stream walks four K chunks per iteration (caller: pair kernel otherwise)
-  static const int env_ib = [] { const char* e = getenv("GLR_K1_IMG_BLOCK"); return e ? atoi(e) : 0; }();
-  p.img_block = env_ib > 0 ? env_ib : 4;
-  const int per_xcd = ((p.B_img + 7) / 8 + p.img_block - 1) / p.img_block * p.img_block;
-  const int grid = per_xcd * 8 * p.n_items * 2;
-#ifdef GLR_ABLATE
-  { const char* e = getenv("GLR_K1_DBG"); p.dbg = e ? atoi(e) : 0; }
-#endif
+  const int grid = glr_k1_pair_grid(p, 2);
   static GlrLdsAttr la;
   if (glr_ensure_lds(la, (const void*)k_local_attn_t1, LDS_T1) != GLR_OK) return GLR_ELAUNCH;
   hipLaunchKernelGGL(k_local_attn_t1, dim3(grid), dim3(NT1), LDS_T1, (hipStream_t)stream, p);

@@ -24,11 +24,8 @@ SYMBOLS = {
     "glr_version": (c_int, []),
     "glr_region_pad": (c_int, [c_int]),
     "glr_tile_capacity": (c_int, [c_int]),
-    "glr_plan_tiles_bound": (c_int, [c_void_p, c_int, c_int]),
-    "glr_plan_tiles": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
-    "glr_plan_items": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
-    "glr_plan_rowflags": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p]),
-    "glr_plan_pair_desc": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p]),
+    "glr_plan_size": (c_int, [c_void_p, c_int, c_int]),
+    "glr_plan_build": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int]),
     "glr_tile_k": (c_int, [c_void_p, c_void_p, c_int, ctypes.c_longlong, c_int, c_void_p]),
     "glr_pack_regions": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
     "glr_pack_regions_tiled": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
@@ -36,13 +33,14 @@ SYMBOLS = {
     "glr_tile_gram": (c_int, [c_void_p, c_void_p, c_int, ctypes.c_longlong, c_int, c_int, c_void_p]),
     "glr_pack_words": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
                                c_int, c_int, c_int, c_void_p]),
-    "glr_local_attn_fwd": (c_int, [c_void_p] * 10 + [c_int, c_void_p, c_int, c_int, c_void_p] + [c_int] * 5 + [c_float] * 3 + [c_int, c_float, c_void_p, c_int,
+    "glr_local_attn_fwd": (c_int, [c_void_p] * 6 + [c_int] * 3 + [c_float] * 3 + [c_int, c_float, c_void_p, c_int,
                                    c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p]),
-                                   # ..., sim, ld, lse, wstat, attn, attn_off, strip, pair_only, img_offset, amean, a1buf, dtype, stream
-    "glr_local_attn_bwd": (c_int, [c_void_p] * 10 + [c_int, c_void_p, c_int, c_void_p] + [c_int] * 5 + [c_float] * 3
+                                   # vt, gram, tp, tnorm, plan, plan_dev, B_img, D, S_eff, temp1..3, agg, eps,
+                                   # sim, ld, lse, wstat, attn, attn_off, strip, pair_only, img_offset, amean, a1buf, dtype, stream
+    "glr_local_attn_bwd": (c_int, [c_void_p] * 6 + [c_int] * 3 + [c_float] * 3
                            + [c_int, c_float, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                               c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
-                                   # sim, dsim, ld, lse, wstat, damean, dattn, attn_off, strip, img_offset,
+                                   # ..., sim, dsim, ld, lse, wstat, damean, dattn, attn_off, strip, img_offset,
                                    # xout, aout, baout, gamma, beta, a1buf, dtype, stream
     "glr_sumsq_blocks": (c_int, [ctypes.c_longlong]),
     "glr_gather_mt": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p]),
@@ -185,85 +183,40 @@ def require_cuda(*tensors):
             raise RuntimeError("the GLoRIA hot path runs on the GPU only (HIP kernels); got a CPU tensor")
 
 
-MAX_PAIR_SEG = 8        # sentences per tile pair (table rows of the pair kernels)
+MAX_PAIR_SEG = 8        # GLR_MAX_PAIR_SEG: sentences per tile pair (table rows of the pair kernels)
+PLAN_HEADER = 64        # GLR_PLAN_HEADER; header words: include/glr.h (GLR_PLAN_*)
 
 
 class TilePlan:
-    """Sentence -> word-slot packing (host planning by glr_plan_tiles + device copies)."""
+    """Sentence -> word-slot packing and K1 work items: glr_plan_build into one int32 buffer (`host`), one upload, and
+    the arrays of include/glr.h as views of the device copy."""
 
     def __init__(self, cap_lens, device, capacity=TILE_WORDS, allow_pairs=True):
         cl = np.ascontiguousarray(np.asarray(cap_lens, dtype=np.int32))
         n = int(cl.shape[0])
         L = lib()
-        bound = L.glr_plan_tiles_bound(cl.ctypes.data_as(c_void_p), n, capacity)
-        if bound <= 0:
-            raise ValueError(f"cap_lens must be in [1, 512] (glr_plan_tiles_bound -> {bound})")
-        slot0 = np.zeros(n, dtype=np.int32)
-        tile_first = np.zeros(bound + 1, dtype=np.int32)
-        order = np.zeros(bound, dtype=np.int32)
-        nsub = np.zeros(bound, dtype=np.int32)
-        pairing = bool(allow_pairs and capacity == TILE_WORDS)
-        nt = L.glr_plan_tiles(cl.ctypes.data_as(c_void_p), n, capacity, MAX_PAIR_SEG if pairing else 0,
-                              slot0.ctypes.data_as(c_void_p),
-                              tile_first.ctypes.data_as(c_void_p), order.ctypes.data_as(c_void_p),
-                              nsub.ctypes.data_as(c_void_p))
-        if nt <= 0:
-            raise ValueError(f"glr_plan_tiles failed ({nt})")
-        singles = np.zeros(nt, dtype=np.int32)
-        pairs = np.zeros(nt, dtype=np.int32)
-        alls = np.zeros(nt, dtype=np.int32)
-        counts = np.zeros(3, dtype=np.int32)
-        rc = L.glr_plan_items(nsub.ctypes.data_as(c_void_p), tile_first.ctypes.data_as(c_void_p), nt,
-                              1 if pairing else 0, MAX_PAIR_SEG,
-                              singles.ctypes.data_as(c_void_p), pairs.ctypes.data_as(c_void_p),
-                              alls.ctypes.data_as(c_void_p), counts.ctypes.data_as(c_void_p))
-        if rc != 0:
-            raise ValueError(f"glr_plan_items failed ({rc})")
-        self.n_single, self.n_pair, self.n_all = (int(c) for c in counts)
-        # pairs that are the two tiles of ONE 65..128-word sentence: a prefix of the pair list (multi-tile sentences
-        # are planned first); they run the 8-wave pair kernel, the rest one workgroup per tile
-        is_long = nsub[pairs[:self.n_pair]] == 2
-        self.n_long_pair = int(is_long.sum())
-        if not bool(is_long[:self.n_long_pair].all()):
-            raise RuntimeError("tile plan: long pairs are expected to lead the pair list")
-        # run boundaries per tile and lane half for the forward pair kernel (full-width tiles only)
-        flags = np.zeros(nt * 8, dtype=np.uint32)
-        if self.n_pair:
-            rc = L.glr_plan_rowflags(cl.ctypes.data_as(c_void_p), slot0.ctypes.data_as(c_void_p),
-                                     tile_first.ctypes.data_as(c_void_p), order.ctypes.data_as(c_void_p),
-                                     nsub.ctypes.data_as(c_void_p), nt, capacity, flags.ctypes.data_as(c_void_p))
-            if rc != 0:
-                raise ValueError(f"glr_plan_rowflags failed ({rc})")
-        self.rowflags_host = flags.reshape(nt, 8)
-        # one 256-byte descriptor per forward pair (sentences + row flags): what a workgroup reads about its pair
-        desc = np.zeros(max(self.n_pair, 1) * 64, dtype=np.int32)
-        if self.n_pair:
-            rc = L.glr_plan_pair_desc(cl.ctypes.data_as(c_void_p), slot0.ctypes.data_as(c_void_p),
-                                      tile_first.ctypes.data_as(c_void_p), order.ctypes.data_as(c_void_p),
-                                      nsub.ctypes.data_as(c_void_p), nt, capacity, pairs.ctypes.data_as(c_void_p),
-                                      self.n_pair, desc.ctypes.data_as(c_void_p))
-            if rc != 0:
-                raise ValueError(f"glr_plan_pair_desc failed ({rc})")
-        self.capacity = capacity
+        size = L.glr_plan_size(cl.ctypes.data_as(c_void_p), n, capacity)
+        if size <= 0:
+            raise ValueError(f"cap_lens must be in [1, 512] (glr_plan_size -> {size})")
+        buf = np.empty(size, dtype=np.int32)
+        used = L.glr_plan_build(cl.ctypes.data_as(c_void_p), n, capacity, 1 if allow_pairs else 0,
+                                buf.ctypes.data_as(c_void_p), size)
+        if used <= 0:
+            raise ValueError(f"glr_plan_build failed ({used})")
+        self.host = host = buf[:used]
+        (self.n_sent, self.n_tiles, self.capacity, n_order, self.n_single, self.n_pair, self.n_long_pair,
+         _) = (int(v) for v in host[:8])
+        self.n_slots = self.n_tiles * TILE_WORDS
+        dev = upload(host, device)
+        names = ("cap_lens", "sent_slot0", "tile_first", "order", "tile_nsub", "single_tile", "pair_tile", "pair_desc")
+        lens = (n, n, self.n_tiles + 1, n_order, self.n_tiles, self.n_single, self.n_pair, self.n_pair * 64)
+        for name, off, ln in zip(names, host[8:16].tolist(), lens):
+            setattr(self, name, dev[off:off + ln])
+        if not self.n_pair:
+            self.pair_desc = None
         self.cap_lens_host = cl
-        self.n_sent, self.n_tiles, self.n_slots = n, nt, nt * TILE_WORDS
-        self.sent_slot0_host = slot0
+        self.sent_slot0_host = host[int(host[9]):int(host[9]) + n]
         self.n_words = int(cl.sum())
-        head = n + n + (nt + 1) + bound + nt + self.n_single + self.n_pair + self.n_all
-        pad = np.zeros((-head) % 64, dtype=np.int32)     # the descriptors start on a 256-byte boundary (16-byte LDS-DMA pieces)
-        pack = np.concatenate([cl, slot0, tile_first[: nt + 1], order, nsub[:nt], singles[:self.n_single],
-                               pairs[:self.n_pair], alls[:self.n_all], pad, desc[:self.n_pair * 64]]).astype(np.int32)
-        dev = upload(pack, device)
-        o = 0
-        self.cap_lens = dev[o:o + n]; o += n
-        self.sent_slot0 = dev[o:o + n]; o += n
-        self.tile_first = dev[o:o + nt + 1]; o += nt + 1
-        self.order = dev[o:o + bound]; o += bound
-        self.tile_nsub = dev[o:o + nt]; o += nt
-        self.single_tile = dev[o:o + self.n_single]; o += self.n_single
-        self.pair_tile = dev[o:o + self.n_pair]; o += self.n_pair
-        self.all_tile = dev[o:o + self.n_all]; o += self.n_all + len(pad)
-        self.pair_desc = dev[o:o + self.n_pair * 64] if self.n_pair else None
         self._dev = dev
         self._word_index = None
 

@@ -18,7 +18,6 @@ Differences that are deliberate and documented in DESIGN.md:
 from typing import List, Optional, Sequence
 
 import numpy as np
-import os
 
 import torch
 
@@ -33,7 +32,6 @@ _COMPUTE_DTYPE = None          # None = follow the input dtype
 # and "k1_flops": algorithmic forward FLOPs of every forward call.
 PROFILE = None
 _DEBUG_HOOK = None          # diagnostics only: called with the K1 backward outputs (tools)
-HANDOVER_A1 = os.environ.get("GLR_K1_A1", "1") != "0"     # forward -> backward hand-over of a1 (A/B switch)
 
 
 class _Range:
@@ -138,17 +136,9 @@ def _pack_operands(img_features, words, no_attn_vec, cap_lens, o):
     return plan, code, vt, vt_t, gram_t, tp, tp_t, tnorm, s_eff, s_pad, shift
 
 
-def _k1_args(plan, vt, gram, tp, tnorm, B, D, s_eff, o, backward=False):
-    head = (N.ptr(vt), N.ptr(gram), N.ptr(tp), N.ptr(tnorm), N.ptr(plan.sent_slot0), N.ptr(plan.cap_lens),
-            N.ptr(plan.tile_first), N.ptr(plan.order), N.ptr(plan.tile_nsub))
-    if backward == "all_single":
-        # extra gradient inputs (regulariser rows / attention maps): every tile through the single-tile kernel
-        items = (N.ptr(plan.all_tile), plan.n_all, None, 0, None)
-    else:
-        items = (N.ptr(plan.single_tile) if plan.n_single else None, plan.n_single,
-                 N.ptr(plan.pair_tile) if plan.n_pair else None, plan.n_pair) \
-            + (() if backward else (plan.n_long_pair,)) + (N.ptr(plan.pair_desc),)
-    return head + items + (plan.n_tiles, plan.n_sent, B, D, s_eff, o.temp1, o.temp2, o.temp3, N.AGG[o.agg], o.eps)
+def _k1_args(plan, vt, gram, tp, tnorm, B, D, s_eff, o):
+    return (N.ptr(vt), N.ptr(gram), N.ptr(tp), N.ptr(tnorm), plan.host.ctypes.data, N.ptr(plan._dev), B, D, s_eff,
+            o.temp1, o.temp2, o.temp3, N.AGG[o.agg], o.eps)
 
 
 class LocalSimFn(torch.autograd.Function):
@@ -183,10 +173,10 @@ class LocalSimFn(torch.autograd.Function):
             attn_off, off_host = plan.attn_offsets(s_eff - strip, dev)
             attn = torch.zeros(int(off_host[-1]), dtype=torch.float32, device=dev)
         amean = torch.empty(B, n_sent, s_pad, dtype=torch.float32, device=dev) if o.want_amean else None
-        # the forward pair kernel hands the word-softmax values to the backward pair kernel (98 KB per image x pair, fp16,
-        # in the kernels' own register order): the backward then skips its score stream
+        # the forward pair kernels hand the word-softmax values to the backward pair kernel (98 KB per image x pair, fp16,
+        # in the kernels' own register order): the backward has no score stream of its own
         a1buf = None
-        if need_grad and plan.n_pair and HANDOVER_A1 and not o.pair_only:
+        if need_grad and plan.n_pair:
             a1buf = torch.empty(B * plan.n_pair * 24576, dtype=torch.int32, device=dev)
         with _Range("k1_fwd"):
             N.check(L.glr_local_attn_fwd(*_k1_args(plan, vt_t, gram_t, tp_t, tnorm, B, D, s_eff, o), N.ptr(sim), n_sent,
@@ -252,10 +242,7 @@ class LocalSimFn(torch.autograd.Function):
             bwd_range = _Range("k1_bwd_op")
             bwd_range.__enter__()
             with _Range("k1_bwd"):
-                # the extra gradient inputs (regulariser rows / attention maps) ride on the pair kernel's a1 hand-over
-                # variant; without the hand-over buffer every tile goes through the single-tile kernel
-                mode = "all_single" if ((dam is not None or dat is not None) and a1buf is None) else True
-                N.check(L.glr_local_attn_bwd(*_k1_args(plan, vt_t, gram_t, tp_t, tnorm, B, D, s_eff, o, mode), N.ptr(sim),
+                N.check(L.glr_local_attn_bwd(*_k1_args(plan, vt_t, gram_t, tp_t, tnorm, B, D, s_eff, o), N.ptr(sim),
                                              N.ptr(g), plan.n_sent, N.ptr(lse), N.ptr(wstat), N.ptr(dam), N.ptr(dat),
                                              N.ptr(dat_off), strip, o.img_offset, N.ptr(xout), N.ptr(aout), N.ptr(baout),
                                              N.ptr(gamma), N.ptr(beta), N.ptr(a1buf), code, N.stream()), "glr_local_attn_bwd")

@@ -60,59 +60,71 @@ int glr_region_pad(int s_eff);
 int glr_tile_capacity(int op_dtype);
 
 /* ------------------------------------------------------------------------------------------
- * Host-side planning: pack sentences into tiles of GLR_TILE_WORDS word slots.
+ * Host-side planning (plain C++, no GPU): pack sentences into tiles of GLR_TILE_WORDS word slots and list the work
+ * items of the K1 kernels, in ONE call that fills ONE int32 buffer.
  * Replaces the per-sentence slicing `words_emb[i, :, :cap_lens[i]]` of the reference loop
  * (gloria_loss.py:116-123): sentence i occupies cap_lens[i] consecutive slots.  A sentence of at
  * most `capacity` words lies inside one tile (first fit, in the given order, at most `capacity`
  * populated slots per tile); a longer one owns ceil(n / capacity) consecutive tiles of its own.
  *
- *   cap_lens[n_sent]    words per sentence (1..GLR_MAX_WORDS)
- *   capacity            glr_tile_capacity(op_dtype)
- *   max_pair_seg        0: plain first fit.  > 1 (the value later given to glr_plan_items): tiles will be paired, a pair
- *                       holding at most that many sentences - the planner then also caps the sentences per tile
- *                       where that lowers the number of work items (a few more, emptier tiles instead of crowded
- *                       tiles that cannot pair), and orders ordinary tiles fewest-sentences-next-to-most
- *   sent_slot0[n_sent]  out: global slot of the sentence's first word (tile * GLR_TILE_WORDS + pos);
- *                       word w of a multi-tile sentence sits at slot0 + (w / capacity) * GLR_TILE_WORDS
- *                       + w % capacity
- *   tile_first[cap]     out: for tile t, index of its first sentence in `order`; [n_tiles] = end.
- *                       Must hold (upper bound on tiles) + 1 ints; glr_plan_tiles_bound gives it.
- *   order[cap]          out: sentence ids in tile order (a multi-tile sentence appears once per tile)
- *   tile_nsub[cap]      out: 0 = ordinary tile, k > 1 = first tile of a k-tile sentence, -1 = its
- *                       continuation tiles
- * returns the number of tiles (>0) or a negative error.
+ *   cap_lens[n_sent]  words per sentence (1..GLR_MAX_WORDS)
+ *   capacity          glr_tile_capacity(op_dtype): 64 or 32
+ *   allow_pairs       non-zero (and capacity == 64): tiles are paired, a pair holding at most GLR_MAX_PAIR_SEG
+ *                     sentences - the planner then also caps the sentences per tile where that lowers the number of
+ *                     work items (a few more, emptier tiles instead of crowded tiles that cannot pair), and orders
+ *                     ordinary tiles fewest-sentences-next-to-most.  Zero, or capacity 32: plain first fit, no pairs.
+ *   plan[plan_ints]   out: GLR_PLAN_HEADER header words, then the arrays, each at the offset (in int32 words from the
+ *                     start of the buffer) the header gives:
+ *     header   [GLR_PLAN_N_SENT] [GLR_PLAN_N_TILES] [GLR_PLAN_CAPACITY] [GLR_PLAN_N_ORDER] [GLR_PLAN_N_SINGLE]
+ *              [GLR_PLAN_N_PAIR] [GLR_PLAN_N_LONG_PAIR] [GLR_PLAN_N_INTS] (words used), the eight offsets
+ *              [GLR_PLAN_OFF_CAP_LENS .. GLR_PLAN_OFF_PAIR_DESC], the rest 0
+ *     cap_lens[n_sent]       copy of the input
+ *     sent_slot0[n_sent]     global slot of the sentence's first word (tile * GLR_TILE_WORDS + pos); word w of a
+ *                            multi-tile sentence sits at slot0 + (w / capacity) * GLR_TILE_WORDS + w % capacity
+ *     tile_first[n_tiles+1]  for tile t, index of its first sentence in `order`; [n_tiles] = n_order
+ *     order[n_order]         sentence ids in tile order (a multi-tile sentence appears once per tile)
+ *     tile_nsub[n_tiles]     0 = ordinary tile, k > 1 = first tile of a k-tile sentence, -1 = its continuation tiles
+ *     single_tile[n_single]  first tile of every un-paired work item (ordinary tile or head of a multi-tile sentence)
+ *     pair_tile[n_pair]      first tile of every pair: two consecutive ordinary tiles, or the two tiles owned by ONE
+ *                            sentence of 65..128 words.  Those long pairs are the first n_long_pair entries (enforced:
+ *                            the K1 entry points route that prefix and the rest to different kernels).  A workgroup
+ *                            streams vt[b] and gram[b] once for the 128 words of a pair (the streams are the bound).
+ *     pair_desc[n_pair][64]  starts on a multiple of 64 words.  Per pair ONE 256-byte record - what a workgroup of the
+ *                            pair kernels reads (coalesced, once) instead of walking the arrays above: [0] sentences
+ *                            (<= GLR_MAX_PAIR_SEG), [1] long-pair flag, [8..15] sentence ids, [16..23] first slot in the
+ *                            pair (0..127), [24..31] words, [32..39] / [40..47] row flags of tile A / B, rest 0.
+ *                            Row flags (uint32 bit masks, bit k = row k of a lane half; in the pair kernels one wave
+ *                            holds all 64 word slots of a tile for its region columns, 32 rows per lane half in word
+ *                            order, a sentence is a run of rows and the kernel acts only where a run starts or ends):
+ *                            [0..1] run starts of half 0 / 1, [2..3] run ends, [4..5] the run holding the sentence's
+ *                            first word, [6..7] reserved.  They stand for the slice boundaries of the reference loop
+ *                            (gloria_loss.py:122) inside a packed tile.
+ * glr_plan_size  -> upper bound of the words glr_plan_build writes for these sentences (header included), or a negative
+ *                   error.
+ * glr_plan_build -> the number of words used (> 0, also in the header), or a negative error; GLR_EINVAL when plan_ints
+ *                   is smaller than that, a length is outside 1..GLR_MAX_WORDS, capacity is not 32 / 64 or a pointer is
+ *                   NULL.  The device kernels take a device copy of the first `words used` words.
  */
-int glr_plan_tiles_bound(const int32_t* cap_lens, int n_sent, int capacity);
-int glr_plan_tiles(const int32_t* cap_lens, int n_sent, int capacity, int max_pair_seg, int32_t* sent_slot0,
-                   int32_t* tile_first, int32_t* order, int32_t* tile_nsub);
-
-/* Work items of the local-attention kernels.  With allow_pairs, two consecutive ordinary tiles that hold
- * at most max_pair_seg (<= 8) sentences IN TOTAL become ONE forward work item: a workgroup then streams vt[b] and
- * gram[b] once for 128 words (the streams are the bound).  Outputs (each must hold n_tiles ints):
- *   single_tile  first tile of every un-paired item (ordinary tile or head of a multi-tile sentence)
- *   pair_tile    first tile of every pair: two ordinary tiles, or the two tiles owned by ONE sentence of 65..128 words
- *   all_tile     every item-head tile with pairs expanded (the backward kernel works tile by tile)
- *   counts[3]    number of entries of the three lists
- */
-int glr_plan_items(const int32_t* tile_nsub, const int32_t* tile_first, int n_tiles, int allow_pairs,
-                   int max_pair_seg, int32_t* single_tile, int32_t* pair_tile, int32_t* all_tile, int32_t* counts);
-
-/* Row flags of the forward pair kernel (host).  In that kernel one wave holds all 64 word slots of a tile for its
- * region columns, 32 rows per lane half in word order; a sentence is a run of rows, and the kernel acts only where
- * a run starts or ends.  flags[n_tiles][8] (uint32, bit k = row k of the lane half): [0..1] run starts of half
- * 0 / 1, [2..3] run ends, [4..5] the run holding the sentence's first word, [6..7] reserved.  Replaces the
- * per-sentence slice boundaries of the reference loop (gloria_loss.py:122) inside a packed tile.  capacity must be
- * GLR_TILE_WORDS. */
-int glr_plan_rowflags(const int32_t* cap_lens, const int32_t* sent_slot0, const int32_t* tile_first,
-                      const int32_t* order, const int32_t* tile_nsub, int n_tiles, int capacity, uint32_t* flags);
-
-/* Pair descriptors (host): per forward pair ONE 256-byte record with its sentences (ids, first slots, lengths) and the
- * row flags of both tiles - what a workgroup of the pair kernel reads (coalesced, once) instead of walking tile_first /
- * order / sent_slot0 / cap_lens.  desc[n_pair][64] int32: [0] sentences (<= 8), [1] long-pair flag, [8..15] sentence
- * ids, [16..23] first slot in the pair, [24..31] words, [32..39] / [40..47] glr_plan_rowflags of tile A / B. */
-int glr_plan_pair_desc(const int32_t* cap_lens, const int32_t* sent_slot0, const int32_t* tile_first,
-                       const int32_t* order, const int32_t* tile_nsub, int n_tiles, int capacity,
-                       const int32_t* pair_tile, int n_pair, int32_t* desc);
+#define GLR_MAX_PAIR_SEG 8      /* sentences per tile pair (table rows of the pair kernels) */
+#define GLR_PLAN_HEADER 64      /* int32 words in front of the arrays (256 bytes: pair_desc keeps its alignment) */
+#define GLR_PLAN_N_SENT 0
+#define GLR_PLAN_N_TILES 1
+#define GLR_PLAN_CAPACITY 2
+#define GLR_PLAN_N_ORDER 3
+#define GLR_PLAN_N_SINGLE 4
+#define GLR_PLAN_N_PAIR 5
+#define GLR_PLAN_N_LONG_PAIR 6
+#define GLR_PLAN_N_INTS 7
+#define GLR_PLAN_OFF_CAP_LENS 8
+#define GLR_PLAN_OFF_SENT_SLOT0 9
+#define GLR_PLAN_OFF_TILE_FIRST 10
+#define GLR_PLAN_OFF_ORDER 11
+#define GLR_PLAN_OFF_TILE_NSUB 12
+#define GLR_PLAN_OFF_SINGLE_TILE 13
+#define GLR_PLAN_OFF_PAIR_TILE 14
+#define GLR_PLAN_OFF_PAIR_DESC 15
+int glr_plan_size(const int32_t* cap_lens, int n_sent, int capacity);
+int glr_plan_build(const int32_t* cap_lens, int n_sent, int capacity, int allow_pairs, int32_t* plan, int plan_ints);
 
 /* ------------------------------------------------------------------------------------------
  * Operand packing (device).  HBM-bound layout/convert kernels.
@@ -157,18 +169,17 @@ int glr_pack_words(const void* words_emb, int in_dtype, const int32_t* sent_slot
  *
  *   vt, gram     packed regions of the B_img LOCAL images and their Gram matrices, K-TILED (glr_tile_k, rows = S_pad)
  *   tp, tnorm    packed words of ALL sentences (glr_pack_words); tp K-TILED (glr_tile_k, rows = 64)
- *   sent_slot0, cap_lens   [n_sent] device int32 (same arrays as given to glr_pack_words)
- *   tile_first, order, tile_nsub   device int32 copies of the glr_plan_tiles outputs
- *   single_tile/n_single, pair_tile/n_pair (fwd), item_tile/n_items (bwd: the all_tile list)
- *                device int32 copies of the glr_plan_items outputs
- *   n_long_pair  (fwd) how many LEADING entries of pair_tile are the two tiles of ONE 65..128-word sentence (the planner
- *                lists multi-tile sentences first).  Those run the 8-wave pair kernel; the ordinary pairs (two whole
- *                tiles) run one 4-wave workgroup per tile, two workgroups per CU (csrc/glr_local_attn_t1.hip).
- *   pair_desc    (fwd) device copy of the glr_plan_pair_desc output [n_pair][64]; required when n_pair > 0.  The
- *                pair kernels also need S_eff < S_pad and expects gram[b] to carry ONES in row S_pad - 1, columns
- *                r < S_eff (a padded region; glr_tile_gram writes it): the second contraction then delivers
- *                Z_w = sum_r e2[w, r] in output column S_pad - 1.  Every other kernel masks padded regions, so the
- *                same gram serves them and the backward.
+ *   plan         the HOST buffer glr_plan_build filled; only its header is read (counts >= 0, every array inside
+ *                n_ints, capacity == glr_tile_capacity(op_dtype), n_long_pair <= n_pair - else GLR_EINVAL)
+ *   plan_dev     DEVICE copy of the same buffer (its sent_slot0 / cap_lens are what glr_pack_words took).  Work items:
+ *                single tiles run the single-tile kernel; the first n_long_pair pairs (ONE 65..128-word sentence
+ *                each) run the 8-wave pair kernel; the ordinary pairs (two whole tiles) run one 4-wave workgroup per
+ *                tile, two workgroups per CU (csrc/glr_local_attn_t1.hip; forward, D % 128 == 0 and D >= 256 - else
+ *                the pair kernel too).  The pair kernels are built for bf16 and S_pad == 384, need S_eff < S_pad and
+ *                expect gram[b] to carry ONES in row S_pad - 1, columns r < S_eff (a padded region; glr_tile_gram
+ *                writes it): the second contraction then delivers Z_w = sum_r e2[w, r] in output column S_pad - 1.
+ *                Every other kernel masks padded regions, so the same gram serves them and the backward.  Plan
+ *                without pairs (allow_pairs = 0) for any other shape.
  *   sim          fp32 [B_img, ld_sim]; column = sentence id (fwd: out, bwd: in)
  *   lse          fp32 [B_img, n_sent, S_pad]: log-sum-exp over the words of sentence i of the
  *                scores of region r (fwd: optional out, needed by bwd)
@@ -196,30 +207,26 @@ int glr_pack_words(const void* words_emb, int in_dtype, const int32_t* sent_slot
  *                kernel's own second-contraction operand holds it
  *   gamma [B_img, n_slots] fp32              coefficient of T_w in dT (from the word norm)
  * with X2d = xout viewed [n_slots, B_img*S_pad] and vt2d = vt viewed [B_img*S_pad, D].
- *   a1buf  optional, both directions (NULL = none): n_pair * B_img * 98304 bytes.  The forward pair kernel leaves the
- *          word-softmax values a1 of every pair there (fp16, in the pair kernels' own register order - opaque to the
- *          caller); given the same buffer, the backward pair kernel reads them instead of re-streaming vt[b] and the
- *          word tiles for the scores (s = lse + log a1).
- * The backward takes the forward's work items: single tiles and (bf16, 384 regions, no damean / dattn) pairs with
- * their descriptors; with damean / dattn every tile must be passed as a single tile.
+ *   a1buf  n_pair * B_img * 98304 bytes.  The forward pair kernels leave the word-softmax values a1 of every pair there
+ *          (fp16, in the pair kernels' own register order - opaque to the caller); the backward pair kernel reads them
+ *          instead of re-streaming vt[b] and the word tiles for the scores (s = lse + log a1).  Optional in the
+ *          forward (NULL = none: a forward without gradient state).  The backward REQUIRES the buffer its forward
+ *          filled whenever the plan has pairs (GLR_EINVAL otherwise); without pairs it is not read.
+ * The backward takes the forward's work items: single tiles and pairs, with or without damean / dattn.
  */
 int glr_local_attn_fwd(const void* vt, const void* gram, const void* tp, const float* tnorm,
-                       const int32_t* sent_slot0, const int32_t* cap_lens, const int32_t* tile_first,
-                       const int32_t* order, const int32_t* tile_nsub, const int32_t* single_tile, int n_single,
-                       const int32_t* pair_tile, int n_pair, int n_long_pair, const int32_t* pair_desc, int n_tiles,
-                       int n_sent, int B_img, int D, int S_eff, float temp1, float temp2, float temp3, int agg, float eps,
+                       const int32_t* plan, const int32_t* plan_dev,
+                       int B_img, int D, int S_eff, float temp1, float temp2, float temp3, int agg, float eps,
                        float* sim, int ld_sim, float* lse, float* wstat, float* attn, const int64_t* attn_off,
                        int strip, int pair_only, int img_offset, float* amean, void* a1buf, int op_dtype, void* stream);
 
 int glr_local_attn_bwd(const void* vt, const void* gram, const void* tp, const float* tnorm,
-                       const int32_t* sent_slot0, const int32_t* cap_lens, const int32_t* tile_first,
-                       const int32_t* order, const int32_t* tile_nsub, const int32_t* single_tile, int n_single,
-                       const int32_t* pair_tile, int n_pair, const int32_t* pair_desc,
-                       int n_tiles, int n_sent, int B_img, int D, int S_eff, float temp1, float temp2, float temp3,
-                       int agg, float eps, const float* sim, const float* dsim, int ld_sim, const float* lse,
-                       const float* wstat, const float* damean, const float* dattn, const int64_t* attn_off,
-                       int strip, int img_offset, void* xout, void* aout, void* baout, float* gamma, float* beta,
-                       const void* a1buf, int op_dtype, void* stream);
+                       const int32_t* plan, const int32_t* plan_dev,
+                       int B_img, int D, int S_eff, float temp1, float temp2, float temp3, int agg, float eps,
+                       const float* sim, const float* dsim, int ld_sim, const float* lse, const float* wstat,
+                       const float* damean, const float* dattn, const int64_t* attn_off, int strip, int img_offset,
+                       void* xout, void* aout, void* baout, float* gamma, float* beta, const void* a1buf,
+                       int op_dtype, void* stream);
 
 /* K-tiling of the K1 operands (device, HBM-bound copy).  glr_local_attn_fwd / _bwd take vt, gram and tp in
  * the K-TILED layout: every block of `rows` rows (vt, gram: the S_pad rows of one image; tp: the 64 slots of one
@@ -232,7 +239,7 @@ int glr_local_attn_bwd(const void* vt, const void* gram, const void* tp, const f
 int glr_tile_k(const void* src, void* dst, int rows, long long n_blocks, int row_bytes, void* stream);
 /* glr_tile_gram: K-tiling of the Gram matrices gram [B, S_pad, S_pad] (op_dtype) that also writes the ONES ROW the
  * forward pair kernel expects when S_eff < S_pad (row S_pad - 1: ones in columns r < S_eff, zeros after; see
- * tile_rowflags of glr_local_attn_fwd) - the row-major gram stays untouched. */
+ * plan_dev of glr_local_attn_fwd) - the row-major gram stays untouched. */
 int glr_tile_gram(const void* gram, void* gram_t, int S_pad, long long B, int S_eff, int op_dtype, void* stream);
 
 

@@ -25,7 +25,8 @@ def test_library_exports_every_declared_symbol():
     for n in names:
         assert hasattr(handle, n), f"{n} declared in include/glr.h but not exported"
     assert sorted(N.SYMBOLS) == names, "ctypes table and header disagree"
-    assert N.lib().glr_version() == 2
+    assert "glr_plan_size" in names and "glr_plan_build" in names
+    assert N.lib().glr_version() == 3
 
 
 def test_region_pad():
@@ -66,7 +67,7 @@ def test_plan_items_pairing():
     # 5 ordinary tiles worth of 30-word sentences, one 100-word sentence (2 tiles), then many 1-word ones
     lens = [30, 30] * 5 + [100] + [1] * 40
     p = N.TilePlan(lens, "cpu")
-    singles, pairs, alls = p.single_tile.numpy(), p.pair_tile.numpy(), p.all_tile.numpy()
+    singles, pairs = p.single_tile.numpy(), p.pair_tile.numpy()
     nsub = p.tile_nsub.numpy()
     tf = p.tile_first.numpy()
     covered = []
@@ -80,7 +81,6 @@ def test_plan_items_pairing():
     for t in singles:
         covered += list(range(t, t + max(nsub[t], 1)))
     assert sorted(covered) == list(range(p.n_tiles))                       # every tile exactly once
-    assert sorted(alls.tolist()) == sorted([t for t in range(p.n_tiles) if nsub[t] >= 0])
     # fp32 plans (32-word capacity) are never paired
     assert N.TilePlan(lens, "cpu", 32).n_pair == 0
 
@@ -127,3 +127,51 @@ def test_plan_invariants_on_random_caption_lengths():
             order = p.order.numpy()
             seen = np.concatenate([order[tf[t]:tf[t + 1]] for t in range(p.n_tiles) if nsub[t] >= 0])
             assert sorted(seen.tolist()) == list(range(n))                 # every sentence in exactly one tile (run)
+
+
+def test_plan_header_is_consistent():
+    """the header of the plan buffer (include/glr.h, GLR_PLAN_*) on the batches of the invariants test: offsets increasing
+    and inside n_ints, n_ints within glr_plan_size, descriptors on a 64-int boundary, n_long_pair = the leading long pairs,
+    and a buffer one word short is refused"""
+    from gloria import _native as N
+    L = N.lib()
+    rng = np.random.default_rng(123)
+    for trial in range(40):
+        n = int(rng.integers(1, 300))
+        hi = [8, 40, 97, 257, 512][trial % 5]
+        lens = rng.integers(1, hi + 1, size=n).astype(np.int32)
+        for cap in (64, 32):
+            p = N.TilePlan(lens, "cpu", cap)
+            h = p.host
+            n_sent, n_tiles, capacity, n_order, n_single, n_pair, n_long, n_ints = (int(v) for v in h[:8])
+            assert (n_sent, capacity, n_ints) == (n, cap, len(h)) and not h[16:N.PLAN_HEADER].any()
+            assert n_ints <= L.glr_plan_size(lens.ctypes.data_as(ctypes.c_void_p), n, cap)
+            off = [int(v) for v in h[8:16]]
+            ln = [n, n, n_tiles + 1, n_order, n_tiles, n_single, n_pair, 64 * n_pair]
+            assert off[0] == N.PLAN_HEADER and off[7] % 64 == 0 and off[7] + ln[7] == n_ints
+            for a in range(7):
+                assert off[a] + ln[a] <= off[a + 1]                      # increasing, no overlap
+            assert n_order == h[off[2] + n_tiles]                        # tile_first[n_tiles]
+            nsub, pairs = h[off[4]:off[4] + n_tiles], h[off[6]:off[6] + n_pair]
+            lead = 0
+            while lead < n_pair and nsub[pairs[lead]] == 2:
+                lead += 1
+            assert n_long == lead == p.n_long_pair and not (nsub[pairs[lead:]] == 2).any()
+            short = np.zeros(n_ints - 1, dtype=np.int32)
+            assert L.glr_plan_build(lens.ctypes.data_as(ctypes.c_void_p), n, cap, 1, short.ctypes.data_as(ctypes.c_void_p),
+                                    n_ints - 1) == -1                    # GLR_EINVAL
+            assert not short.any()                                       # and nothing was written
+
+
+def test_planner_is_clean_under_address_and_ub_sanitizers():
+    """csrc/plan_check.cpp (its own main, glr_plan.cpp compiled in, ASan + UBSan linked statically) on seeded random
+    batches with heap buffers of exactly glr_plan_size words; run once as a child process"""
+    import shutil
+    import subprocess
+    cxx = next((c for c in (os.environ.get("CXX"), "g++", "c++", "clang++") if c and shutil.which(c)), None)
+    if cxx is None:
+        pytest.skip("no host C++ compiler")
+    csrc = os.path.join(ROOT, "gloria-nlp-project_amd", "csrc")
+    subprocess.run(["make", "-C", csrc, "plan_check", f"HOSTCXX={cxx}"], check=True, capture_output=True)
+    r = subprocess.run([os.path.join(csrc, "build", "plan_check")], capture_output=True, text=True)
+    assert r.returncode == 0, r.stdout + r.stderr

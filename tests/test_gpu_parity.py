@@ -315,6 +315,33 @@ def test_bf16_shapes_forward_backward_vs_oracle(name):
         assert rel < BF16_GRAD_REL, (label, rel)
 
 
+def test_bf16_mixed_work_items_forward_backward_vs_oracle():
+    """One bf16 plan at 361 regions whose work items are of several kinds at once: a 200-word sentence (four tiles, one
+    single-tile-kernel item worked in sweeps), two long pairs (100 and 70 words: one sentence owning two tiles), and two
+    ordinary pairs (64 + 64 words; 40 + 33 + 23 + 9 + 5 + 2 + 1 words over two tiles), forward and backward at D = 256 (the
+    ordinary pairs' forward runs one workgroup per tile).  sim and both gradients against the oracle on the rounded
+    inputs, in the bf16 bands of test_attention_regularisers_vs_oracle."""
+    B, D, H, W, L = 12, 256, 19, 19, 200
+    cap_lens = [200, 100, 70, 64, 64, 40, 33, 23, 9, 5, 2, 1]
+    seed = 4343
+    img, words = g(gi.normal(seed, B, D, H, W)).bfloat16(), g(gi.normal(seed + 1, B, D, L)).bfloat16()
+    ti, tw = img.clone().requires_grad_(True), words.clone().requires_grad_(True)
+    sim, _, _ = gl().local_similarity(ti, tw, cap_lens, want_attn=False)
+    ri, rw = img.float().cpu().requires_grad_(True), words.float().cpu().requires_grad_(True)
+    want = orc().local_similarity_matrix(ri, rw, cap_lens)
+    print(f"[bf16 mixed items] max |sim - oracle| = {(sim.detach().cpu() - want.detach()).abs().max().item():.4f}")
+    gsim = torch.from_numpy(gi.normal(seed + 5, *sim.shape, std=1.0))
+    (sim * gsim.to(DEV)).sum().backward()
+    (want * gsim).sum().backward()
+    rels = [(label, np.linalg.norm(a.float().cpu().numpy() - b.numpy()) / np.linalg.norm(b.numpy()))
+            for label, a, b in (("img", ti.grad, ri.grad), ("words", tw.grad, rw.grad))]
+    for label, rel in rels:
+        print(f"[bf16 mixed items] grad {label}: relative Frobenius error {rel:.4f}")
+    np.testing.assert_allclose(sim.detach().cpu().numpy(), want.detach().numpy(), rtol=2e-2, atol=2e-3)
+    for label, rel in rels:
+        assert rel < 0.05, (label, rel)
+
+
 # ------------------------------------------------------------------ (3) properties at the bench size
 
 def _bench_inputs(B=256, seed=77):

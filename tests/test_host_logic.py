@@ -168,8 +168,9 @@ def test_unloadable_hyper_parameters_are_reported(tmp_path):
 
 
 def test_plan_rowflags_match_python_restatement():
-    """glr_plan_rowflags: run starts / ends / owners per tile and lane half against a direct Python walk of the
-    slots (row k of half h = slots with ((w >> 2) & 1) == h in word order)"""
+    """row flags in the pair descriptors (plan.host, words [32..47] of every pair): run starts / ends / owners per tile
+    and lane half against a direct Python walk of the slots (row k of half h = slots with ((w >> 2) & 1) == h in word
+    order)"""
     from gloria import _native as N
     rng = np.random.default_rng(5)
     checked = 0
@@ -179,9 +180,13 @@ def test_plan_rowflags_match_python_restatement():
         plan = N.TilePlan(lens, "cpu")
         if not plan.n_pair:
             continue
-        flags = plan.rowflags_host
+        h = plan.host
+        pairs = h[h[14]:h[14] + plan.n_pair]
+        desc = h[h[15]:h[15] + 64 * plan.n_pair].reshape(plan.n_pair, 64)
+        flags = desc[:, 32:48].reshape(2 * plan.n_pair, 8).view(np.uint32)       # tiles pairs[k], pairs[k] + 1
+        tiles = np.stack([pairs, pairs + 1], 1).reshape(-1)
         slot0 = plan.sent_slot0_host
-        want = np.zeros_like(flags)
+        want = np.zeros((plan.n_tiles, 8), dtype=np.uint32)
         row_of = lambda w: 16 * (w >> 5) + 4 * ((w & 31) >> 3) + (w & 3)   # noqa: E731
         for i, ln in enumerate(lens):
             k = (ln + 63) // 64
@@ -197,15 +202,15 @@ def test_plan_rowflags_match_python_restatement():
                     want[t, 2 + hh] |= 1 << row_of(ws[-1])
                     if sub == 0 and ws[0] == a:
                         want[t, 4 + hh] |= 1 << row_of(ws[0])
-        assert np.array_equal(flags, want), (lens, flags, want)
+        assert np.array_equal(flags, want[tiles]), (lens, flags, want[tiles])
         owners = sum(bin(int(x)).count("1") for x in flags[:, 4:6].reshape(-1))
-        assert owners == n                      # exactly one owner run per sentence
+        assert owners == int(desc[:, 0].sum())  # exactly one owner run per sentence of a pair (a long pair holds one)
         checked += 1
     assert checked >= 5
 
 
 def test_planner_caps_sentences_per_tile_when_that_saves_work_items():
-    """glr_plan_tiles with pairing in view: every sentence keeps cap_lens consecutive slots inside one tile, pairs hold
+    """glr_plan_build with pairing in view: every sentence keeps cap_lens consecutive slots inside one tile, pairs hold
     at most 8 sentences, ordinary tiles are contiguous behind the multi-tile runs, and at the bench's caption lengths
     no tile is left unpaired (plain first fit leaves 6 .. 7 crowded tiles that cannot pair)."""
     from gloria import _native as N
