@@ -10,7 +10,14 @@ tensors.  Dropout bits: a counter-based hash of the score's position (two rounds
 epilogues draw their Philox keys (fused_ln._philox_args) - reproducible under torch.manual_seed, not the same stream as
 torch's own dropout.  The epilogues use Philox4x32-10 itself; here it cost 40 quarter-rate integer multiplies per 8
 scores in a kernel that is VALU-bound, so the per-score draw is the cheaper mixer and only the KEY comes from Philox's
-counter.  `GLR_FUSED_ATTN=0` switches the kernels off."""
+counter.  `GLR_FUSED_ATTN=0` switches the kernels off.
+
+Captions of 129 to 512 tokens run the block-streaming kernels of csrc/glr_attn_long.hip (glr_attn_long_fwd / _bwd) through
+the same two autograd functions: lse and the keep bits are sized by Lp = L rounded up to 128 ([B * nh, Lp] and
+[B * nh, Lp, Lp / 32]: 32 KB of keep bits per sentence x head at 512 tokens, held until the backward), and the dropout
+counter is the one documented in include/glr.h.  `GLR_FUSED_ATTN_LONG` (0 / 1, default 1: DESIGN.md has the measurement
+behind it - faster than torch on ragged batches, slower when every key of the padded length is live) switches only that
+range; with it off those lengths run torch's scaled_dot_product_attention as every other unsupported case does."""
 
 import math
 import os
@@ -22,7 +29,9 @@ from .. import _native as N
 from .rng import philox_args
 
 ENABLED = os.environ.get("GLR_FUSED_ATTN", "1") != "0"
+LONG_ENABLED = os.environ.get("GLR_FUSED_ATTN_LONG", "1") != "0"
 _MAX_L = None
+_MAX_L_LONG = None
 
 
 def _max_tokens():
@@ -32,18 +41,38 @@ def _max_tokens():
     return _MAX_L
 
 
+def _long_max_tokens():
+    global _MAX_L_LONG
+    if _MAX_L_LONG is None:
+        _MAX_L_LONG = int(N.lib().glr_attn_long_max_tokens())
+    return _MAX_L_LONG
+
+
+def _length_ok(L):
+    """the short kernels up to 128 tokens, the block-streaming ones behind their own switch up to 512"""
+    return L <= _max_tokens() or (LONG_ENABLED and L <= _long_max_tokens())
+
+
+def _entry(L):
+    """(forward, backward, name, rows of lse / keep) of the kernel pair that runs L tokens"""
+    L_ = N.lib()
+    if L <= _max_tokens():
+        return L_.glr_attn_fwd, L_.glr_attn_bwd, "glr_attn", 128
+    return L_.glr_attn_long_fwd, L_.glr_attn_long_bwd, "glr_attn_long", (L + 127) // 128 * 128
+
+
 class _SelfAttn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, q, k, v, key_mask, nh, p, scale):
-        L_ = N.lib()
         B, L, H = q.shape
+        fwd, _, name, Lp = _entry(L)
         dev = q.device
         o = torch.empty_like(q)
-        lse = torch.empty(B * nh, 128, dtype=torch.float32, device=dev)
-        keep = torch.empty(B * nh, 128, 4, dtype=torch.int32, device=dev) if p > 0 else None
+        lse = torch.empty(B * nh, Lp, dtype=torch.float32, device=dev)
+        keep = torch.empty(B * nh, Lp, Lp // 32, dtype=torch.int32, device=dev) if p > 0 else None
         seed, off, cell = philox_args(dev) if p > 0 else (0, 0, None)
-        N.check(L_.glr_attn_fwd(N.ptr(q), N.ptr(k), N.ptr(v), N.ptr(key_mask), B, nh, L, H, H, float(scale), float(p), seed, off,
-                                cell, N.ptr(o), N.ptr(lse), N.ptr(keep), N.stream()), "glr_attn_fwd")
+        N.check(fwd(N.ptr(q), N.ptr(k), N.ptr(v), N.ptr(key_mask), B, nh, L, H, H, float(scale), float(p), seed, off,
+                    cell, N.ptr(o), N.ptr(lse), N.ptr(keep), N.stream()), name + "_fwd")
         ctx.save_for_backward(q, k, v, o, lse, keep, key_mask)
         ctx.meta = (nh, float(p), float(scale))
         return o
@@ -52,12 +81,12 @@ class _SelfAttn(torch.autograd.Function):
     def backward(ctx, d_o):
         q, k, v, o, lse, keep, key_mask = ctx.saved_tensors
         nh, p, scale = ctx.meta
-        L_ = N.lib()
         B, L, H = q.shape
+        _, bwd, name, _ = _entry(L)
         d_o = d_o.to(torch.bfloat16).contiguous()
         dq, dk, dv = torch.empty_like(q), torch.empty_like(q), torch.empty_like(q)
-        N.check(L_.glr_attn_bwd(N.ptr(q), N.ptr(k), N.ptr(v), N.ptr(o), N.ptr(d_o), N.ptr(key_mask), N.ptr(lse), N.ptr(keep),
-                                B, nh, L, H, H, scale, p, N.ptr(dq), N.ptr(dk), N.ptr(dv), N.stream()), "glr_attn_bwd")
+        N.check(bwd(N.ptr(q), N.ptr(k), N.ptr(v), N.ptr(o), N.ptr(d_o), N.ptr(key_mask), N.ptr(lse), N.ptr(keep),
+                    B, nh, L, H, H, scale, p, N.ptr(dq), N.ptr(dk), N.ptr(dv), N.stream()), name + "_bwd")
         return dq, dk, dv, None, None, None, None
 
 
@@ -67,18 +96,17 @@ class _SelfAttnPacked(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, qkv, key_mask, nh, p, scale):
-        L_ = N.lib()
         B, L, H3 = qkv.shape
         H = H3 // 3
+        fwd, _, name, Lp = _entry(L)
         dev = qkv.device
         o = torch.empty(B, L, H, dtype=qkv.dtype, device=dev)
-        lse = torch.empty(B * nh, 128, dtype=torch.float32, device=dev)
-        keep = torch.empty(B * nh, 128, 4, dtype=torch.int32, device=dev) if p > 0 else None
+        lse = torch.empty(B * nh, Lp, dtype=torch.float32, device=dev)
+        keep = torch.empty(B * nh, Lp, Lp // 32, dtype=torch.int32, device=dev) if p > 0 else None
         seed, off, cell = philox_args(dev) if p > 0 else (0, 0, None)
         base = qkv.data_ptr()
-        N.check(L_.glr_attn_fwd(N.c_void_p(base), N.c_void_p(base + 2 * H), N.c_void_p(base + 4 * H), N.ptr(key_mask), B, nh, L, H3, H,
-                                float(scale), float(p), seed, off, cell, N.ptr(o), N.ptr(lse), N.ptr(keep), N.stream()),
-                "glr_attn_fwd")
+        N.check(fwd(N.c_void_p(base), N.c_void_p(base + 2 * H), N.c_void_p(base + 4 * H), N.ptr(key_mask), B, nh, L, H3, H,
+                    float(scale), float(p), seed, off, cell, N.ptr(o), N.ptr(lse), N.ptr(keep), N.stream()), name + "_fwd")
         ctx.save_for_backward(qkv, o, lse, keep, key_mask)
         ctx.meta = (nh, float(p), float(scale))
         return o
@@ -87,21 +115,21 @@ class _SelfAttnPacked(torch.autograd.Function):
     def backward(ctx, d_o):
         qkv, o, lse, keep, key_mask = ctx.saved_tensors
         nh, p, scale = ctx.meta
-        L_ = N.lib()
         B, L, H3 = qkv.shape
         H = H3 // 3
+        _, bwd, name, _ = _entry(L)
         d_o = d_o.to(torch.bfloat16).contiguous()
         dqkv = torch.empty_like(qkv)
         base, dbase = qkv.data_ptr(), dqkv.data_ptr()
-        N.check(L_.glr_attn_bwd(N.c_void_p(base), N.c_void_p(base + 2 * H), N.c_void_p(base + 4 * H), N.ptr(o), N.ptr(d_o),
-                                N.ptr(key_mask), N.ptr(lse), N.ptr(keep), B, nh, L, H3, H, scale, p, N.c_void_p(dbase),
-                                N.c_void_p(dbase + 2 * H), N.c_void_p(dbase + 4 * H), N.stream()), "glr_attn_bwd")
+        N.check(bwd(N.c_void_p(base), N.c_void_p(base + 2 * H), N.c_void_p(base + 4 * H), N.ptr(o), N.ptr(d_o),
+                    N.ptr(key_mask), N.ptr(lse), N.ptr(keep), B, nh, L, H3, H, scale, p, N.c_void_p(dbase),
+                    N.c_void_p(dbase + 2 * H), N.c_void_p(dbase + 4 * H), N.stream()), name + "_bwd")
         return dqkv, None, None, None, None
 
 
 def _fusable(q, k, v, key_mask, nh):
     B, L, H = q.shape
-    return (ENABLED and q.is_cuda and q.dtype == k.dtype == v.dtype == torch.bfloat16 and H == nh * 64 and L <= _max_tokens()
+    return (ENABLED and q.is_cuda and q.dtype == k.dtype == v.dtype == torch.bfloat16 and H == nh * 64 and _length_ok(L)
             and q.is_contiguous() and k.is_contiguous() and v.is_contiguous()
             and (key_mask is None or (key_mask.dtype == torch.bool and tuple(key_mask.shape) == (B, L) and key_mask.is_contiguous())))
 
@@ -109,12 +137,15 @@ def _fusable(q, k, v, key_mask, nh):
 def packed_fusable(x, nh, hidden, L, key_mask):
     """whether BertSelfAttention may run ONE query|key|value Linear and the packed kernels on input x"""
     return (ENABLED and x.is_cuda and torch.is_autocast_enabled("cuda") and torch.get_autocast_dtype("cuda") == torch.bfloat16
-            and hidden == nh * 64 and L <= _max_tokens()
+            and hidden == nh * 64 and _length_ok(L)
             and (key_mask is None or (key_mask.dtype == torch.bool and key_mask.is_contiguous())))
 
 
 def self_attention_packed(qkv, key_mask, nh, p, training):
     """qkv: bf16 [B, L, 3H] (query | key | value columns) -> context [B, L, H]"""
+    if not _length_ok(qkv.shape[1]):                        # a length no enabled kernel takes: the three column blocks
+        q, k, v = (t.contiguous() for t in qkv.split(qkv.shape[2] // 3, dim=-1))
+        return self_attention(q, k, v, key_mask, nh, p, training)
     return _SelfAttnPacked.apply(qkv.contiguous(), key_mask, nh, p if training else 0.0, 1.0 / 8.0)
 
 

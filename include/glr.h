@@ -448,6 +448,33 @@ int glr_attn_bwd(const void* q, const void* k, const void* v, const void* o, con
                  const float* lse, const uint32_t* keep, int B, int n_heads, int L, int ld, int ld_o, float scale, float p_drop,
                  void* dq, void* dk, void* dv, void* stream);
 
+/* The same operation for captions of up to glr_attn_long_max_tokens() = 512 tokens (1 <= L <= 512; csrc/glr_attn_long.hip):
+ * one workgroup per (sentence, head, 128-row block) and pass, the other side streamed through LDS in 128-token blocks
+ * (forward: two sweeps over the key blocks, row maximum / sum first, then P and P V; backward: a query pass over key
+ * blocks and a key pass over query blocks with dK / dV in registers).  No atomics and no sums across workgroups: results
+ * are bitwise reproducible.  Parameters as glr_attn_fwd / glr_attn_bwd except, with Lp = L rounded up to a multiple of 128:
+ *   lse   fp32 [B * n_heads, Lp];
+ *   keep  uint32 [B * n_heads, Lp, Lp / 32]: key 32 j + i of query row r = bit i of word (r, j); NULL when p_drop == 0
+ *         (Lp * Lp / 8 bytes per sentence x head: 32 KB at L = 512).  Masked keys behind the last live key of a
+ *         128-key block are not computed: their words (32-key granularity) are neither written by the
+ *         forward nor read by the backward, and rows >= L carry no information.
+ * Dropout bits: the keyed hash of the short kernels, hash32(ctr) = mix32(mix32(ctr ^ k0) + k1), mix32(x): x ^= x >> 16,
+ * x *= 0x7feb352d, x ^= x >> 15, x *= 0x846ca68b, x ^= x >> 16; with (s, o) = (seed, offset) or (rng_cell[0], rng_cell[1] +
+ * offset) as 64-bit values: k0 = lo(s) ^ (lo(o) * 0x9E3779B9), k1 = hi(s) ^ (hi(o) * 0x85EBCA6B) ^ 0xC2B2AE35.  The
+ * score of head index g = b * n_heads + h, query row r and key c draws (all arithmetic modulo 2^32)
+ *   ctr = ((g * 512 + r) * 4 + (c >> 7)) * 64 + 2 * (c & 31) + ((c >> 6) & 1)
+ *   r16 = bits 16..31 of hash32(ctr) if c & 32, else bits 0..15;   keep iff r16 >= (unsigned)(p_drop * 65536 + 0.5)
+ * - a function of (g, r, c) and the key alone, not of B, L or the launch geometry (it is NOT the short kernels' counter:
+ * the two entry-point pairs draw different bits for the same position).
+ */
+int glr_attn_long_max_tokens(void);
+int glr_attn_long_fwd(const void* q, const void* k, const void* v, const uint8_t* key_mask, int B, int n_heads, int L, int ld,
+                      int ld_o, float scale, float p_drop, unsigned long long seed, unsigned long long offset,
+                      const unsigned long long* rng_cell, void* o, float* lse, uint32_t* keep, void* stream);
+int glr_attn_long_bwd(const void* q, const void* k, const void* v, const void* o, const void* d_o, const uint8_t* key_mask,
+                      const float* lse, const uint32_t* keep, int B, int n_heads, int L, int ld, int ld_o, float scale,
+                      float p_drop, void* dq, void* dk, void* dv, void* stream);
+
 /* ------------------------------------------------------------------------------------------
  * Image half of the collate function: replaces, for a ragged batch of single-channel images,
  *   original_tensor_to_numpy_image   gloria/datasets/mimic_for_gloria.py:36-42  (min-max -> uint8, truncating)
