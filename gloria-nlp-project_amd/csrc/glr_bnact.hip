@@ -18,6 +18,10 @@
 //   channel): bitwise reproducible.
 // * apply passes: short workgroups (256 threads x 4 vectors), and they walk the tensor in the OPPOSITE direction of the
 //   reduce pass in front of them, so the tail the reduce pass touched last is still in the 256 MB Infinity Cache.
+//
+// Eval mode without autograd (validation, retrieval, zero-shot): glr_bn_infer is the apply pass alone with scale / shift
+// from the running statistics - one launch, 2E (3E), nothing written but y - and glr_bn_relu_maxpool3s2_infer folds
+// the stem's BatchNorm + ReLU into the max-pool's reads.
 #include "glr_common.h"
 
 namespace {
@@ -240,6 +244,58 @@ __global__ void __launch_bounds__(BN_NT) k_bn_apply(const E* __restrict__ x, con
   }
 }
 
+// per-channel scale / shift of eval-mode BatchNorm from the running statistics, in fp32 (shared by the two inference
+// kernels: the fused stem equals their composition bitwise only if both form sc / sh by the same expression)
+__device__ __forceinline__ void bn_infer_coef(const float* __restrict__ gamma, const float* __restrict__ beta,
+                                              const float* __restrict__ run_mean, const float* __restrict__ run_var,
+                                              int c0, float eps, float (&sc)[8], float (&sh)[8]) {
+#pragma unroll
+  for (int i = 0; i < 8; ++i) {
+    sc[i] = gamma[c0 + i] / sqrtf(run_var[c0 + i] + eps);
+    sh[i] = __builtin_fmaf(-run_mean[c0 + i], sc[i], beta[c0 + i]);      // explicit: no contraction left to the compiler
+  }
+}
+
+// eval-mode apply: y = relu?( x sc + sh (+ residual) ), sc = gamma / sqrt(run_var + eps), sh = beta - run_mean sc.
+// No statistics pass in front of it: the one launch of a site, k_bn_apply's indexing (a thread keeps its 8 channels).
+template <typename E, bool RESID>
+__global__ void __launch_bounds__(BN_NT) k_bn_infer(const E* __restrict__ x, const E* __restrict__ res,
+                                                    const float* __restrict__ gamma, const float* __restrict__ beta,
+                                                    const float* __restrict__ run_mean, const float* __restrict__ run_var,
+                                                    long long n_vec, int C, float eps, int relu, E* __restrict__ y) {
+  constexpr int UN = 4 >> ElemTraits<E>::SHIFT;
+  const unsigned cpr = (unsigned)C / 8u;                     // a power of two <= 256: a thread keeps its channels
+  const int c0 = (int)(threadIdx.x & (cpr - 1)) * 8;
+  const long long v0 = (long long)blockIdx.x * (BN_NT * UN) + threadIdx.x;
+  Vec8<E> xr[UN], rr[UN];
+#pragma unroll
+  for (int u = 0; u < UN; ++u) {
+    const long long v = v0 + u * BN_NT;
+    if (v < n_vec) {
+      xr[u] = ld8(x + v * 8);
+      if (RESID) rr[u] = ld8(res + v * 8);
+    }
+  }
+  float sc[8], sh[8];
+  bn_infer_coef(gamma, beta, run_mean, run_var, c0, eps, sc, sh);
+#pragma unroll
+  for (int u = 0; u < UN; ++u) {
+    const long long v = v0 + u * BN_NT;
+    if (v < n_vec) {
+      float xv[8], rv[8], o[8];
+      un8(xr[u], xv);
+      if (RESID) un8(rr[u], rv);
+#pragma unroll
+      for (int i = 0; i < 8; ++i) {
+        float z = __builtin_fmaf(xv[i], sc[i], sh[i]);
+        if (RESID) z += rv[i];
+        o[i] = relu ? fmaxf(z, 0.f) : z;
+      }
+      st8(y + v * 8, o);
+    }
+  }
+}
+
 // backward apply: dx = (dz - mean(dz) - xhat mean(dz xhat)) invstd gamma.  RESID: `dy` is the dz the reduce pass wrote.
 template <typename E, bool RESID>
 __global__ void __launch_bounds__(BN_NT) k_bn_bwd_apply(const E* __restrict__ x, const E* __restrict__ dy,
@@ -412,6 +468,34 @@ extern "C" int glr_bn_act_bwd(const void* x, const void* dy, const void* dy2, co
   return GLR_EDTYPE;
 }
 
+template <typename E>
+int bn_infer_launch(const void* x, const void* residual, const float* gamma, const float* beta, const float* run_mean,
+                    const float* run_var, long long R, int C, float eps, int relu, void* y, hipStream_t st) {
+  constexpr int UNA = 4 >> ElemTraits<E>::SHIFT;
+  const long long n_vec = R * C / 8;
+  const long long grid = (n_vec + BN_NT * UNA - 1) / (BN_NT * UNA);
+  if (grid > 0x7fffffffLL) return GLR_EINVAL;
+  if (residual)
+    hipLaunchKernelGGL((k_bn_infer<E, true>), dim3((unsigned)grid), dim3(BN_NT), 0, st, (const E*)x, (const E*)residual,
+                       gamma, beta, run_mean, run_var, n_vec, C, eps, relu, (E*)y);
+  else
+    hipLaunchKernelGGL((k_bn_infer<E, false>), dim3((unsigned)grid), dim3(BN_NT), 0, st, (const E*)x, (const E*)nullptr,
+                       gamma, beta, run_mean, run_var, n_vec, C, eps, relu, (E*)y);
+  GLR_CHECK_LAUNCH();
+  return GLR_OK;
+}
+
+extern "C" int glr_bn_infer(const void* x, const void* residual, const float* gamma, const float* beta,
+                            const float* run_mean, const float* run_var, long long R, int C, float eps, int relu,
+                            void* y, int dtype, void* stream) {
+  if (!x || !gamma || !beta || !run_mean || !run_var || !y || !bn_shape_ok(R, C)) return GLR_EINVAL;
+  hipStream_t st = (hipStream_t)stream;
+  if (dtype == GLR_BF16)
+    return bn_infer_launch<unsigned short>(x, residual, gamma, beta, run_mean, run_var, R, C, eps, relu, y, st);
+  if (dtype == GLR_F32) return bn_infer_launch<float>(x, residual, gamma, beta, run_mean, run_var, R, C, eps, relu, y, st);
+  return GLR_EDTYPE;
+}
+
 // ------------------------------------------------------------------------------------------
 // MaxPool2d(3, stride 2, padding 1) of the ResNet stem on channels-last bf16, forward and backward.  torch's NHWC kernels
 // keep an int64 argmax per output element (0.74 GB for the 0.18 GB output here) and the backward zero-fills the 0.74 GB
@@ -481,6 +565,49 @@ __global__ void __launch_bounds__(256) k_maxpool3s2_bwd(const unsigned short* __
     }
   stv(dx + i * 8, pack8(acc));
 }
+
+// The stem without autograd: eval-mode BatchNorm + ReLU + the max-pool above in ONE pass over the conv1 output (the
+// normalised [B, 64, 150, 150] tensor is never written, and no argmax byte: nobody runs a backward).  Candidates are
+// relu(fma(x, sc, sh)) in fp32 by k_bn_infer's expression, scanned like k_maxpool3s2_fwd; ONE rounding to bf16 at the
+// store.  Rounding is monotone and every candidate is >= 0 (no NaN survives fmaxf), so the result is bitwise
+// k_maxpool3s2_fwd(k_bn_infer(x)).
+__global__ void __launch_bounds__(256) k_bn_relu_maxpool3s2_infer(const unsigned short* __restrict__ x,
+                                                                  const float* __restrict__ gamma, const float* __restrict__ beta,
+                                                                  const float* __restrict__ run_mean,
+                                                                  const float* __restrict__ run_var, int H, int W, int C, int Ho,
+                                                                  int Wo, float eps, long long total,
+                                                                  unsigned short* __restrict__ y) {
+  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;       // (n, oh, ow, channel group of 8)
+  if (i >= total) return;
+  const int cg = C >> 3;
+  const int g = (int)(i % cg);
+  long long t = i / cg;
+  const int ow = (int)(t % Wo); t /= Wo;
+  const int oh = (int)(t % Ho);
+  const long long n = t / Ho;
+  float sc[8], sh[8], best[8];
+  bn_infer_coef(gamma, beta, run_mean, run_var, g * 8, eps, sc, sh);
+#pragma unroll
+  for (int e = 0; e < 8; ++e) best[e] = -INFINITY;           // the window centre is always inside: never stored
+#pragma unroll
+  for (int kh = 0; kh < 3; ++kh) {
+    const int h = 2 * oh - 1 + kh;
+    if (h < 0 || h >= H) continue;
+#pragma unroll
+    for (int kw = 0; kw < 3; ++kw) {
+      const int w = 2 * ow - 1 + kw;
+      if (w < 0 || w >= W) continue;
+      float v[8];
+      unpack8(ldv(x + ((n * H + h) * W + w) * C + g * 8), v);
+#pragma unroll
+      for (int e = 0; e < 8; ++e) {
+        const float z = fmaxf(__builtin_fmaf(v[e], sc[e], sh[e]), 0.f);
+        if (z > best[e]) best[e] = z;
+      }
+    }
+  }
+  stv(y + i * 8, pack8(best));
+}
 }  // namespace
 
 extern "C" int glr_maxpool3s2_fwd(const void* x, int B, int H, int W, int C, void* y, uint8_t* idx, void* stream) {
@@ -489,6 +616,21 @@ extern "C" int glr_maxpool3s2_fwd(const void* x, int B, int H, int W, int C, voi
   const long long total = (long long)B * Ho * Wo * (C / 8);
   hipLaunchKernelGGL(k_maxpool3s2_fwd, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
                      (const unsigned short*)x, H, W, C, Ho, Wo, total, (unsigned short*)y, idx);
+  GLR_CHECK_LAUNCH();
+  return GLR_OK;
+}
+
+extern "C" int glr_bn_relu_maxpool3s2_infer(const void* x, const float* gamma, const float* beta, const float* run_mean,
+                                            const float* run_var, int B, int H, int W, int C, float eps, void* y,
+                                            void* stream) {
+  if (!x || !gamma || !beta || !run_mean || !run_var || !y || B <= 0 || H <= 0 || W <= 0 || C <= 0 || C % 8 != 0)
+    return GLR_EINVAL;
+  const int Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1;
+  const long long total = (long long)B * Ho * Wo * (C / 8);
+  if ((total + 255) / 256 > 0x7fffffffLL) return GLR_EINVAL;
+  hipLaunchKernelGGL(k_bn_relu_maxpool3s2_infer, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+                     (const unsigned short*)x, gamma, beta, run_mean, run_var, H, W, C, Ho, Wo, eps, total,
+                     (unsigned short*)y);
   GLR_CHECK_LAUNCH();
   return GLR_OK;
 }

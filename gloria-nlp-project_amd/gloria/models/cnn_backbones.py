@@ -11,7 +11,7 @@ import warnings
 import torch
 import torch.nn as nn
 
-from .fused_bn import SkipPair, fused_bn_act, fused_maxpool
+from .fused_bn import SkipPair, fused_bn_act, fused_stem
 
 
 class Identity(nn.Module):
@@ -93,7 +93,7 @@ class ResNet50(nn.Module):
         return _Stage(*layers)
 
     def forward(self, x):
-        x = fused_maxpool(self.maxpool, fused_bn_act(self.bn1, self.conv1(x)))
+        x = fused_stem(self.bn1, self.maxpool, self.conv1(x))
         x = self.layer4(self.layer3(self.layer2(self.layer1(x, fork_out=True), fork_out=True)))
         return self.fc(torch.flatten(self.avgpool(x), 1))
 

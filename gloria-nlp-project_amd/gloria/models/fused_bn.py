@@ -4,10 +4,14 @@
 
 Same parameters, buffers and state_dict keys as nn.BatchNorm2d: `fused_bn_act` is called WITH the nn.BatchNorm2d
 module.  The kernels cover what the training step runs (GPU, channels-last, training mode, power-of-two channel counts;
-bf16 under autocast and - since the end of round 3 - fp32, the parity configuration of BASELINE config 1); every other
-case (eval mode, NCHW, CPU tensors of the host-logic tests) is torch's own BatchNorm + add + relu - the same operator
-from the library, not a CPU fallback of the loss path.
-`GLR_FUSED_BN=0` switches the kernels off (A/B measurements)."""
+bf16 under autocast and - since the end of round 3 - fp32, the parity configuration of BASELINE config 1) and what the
+readers of images outside it run: eval mode where autograd records nothing (Trainer.evaluate, get_similarities,
+zero-shot, retrieval, the localization callbacks: model.eval() under torch.no_grad()) is ONE launch per site with
+scale / shift from the running statistics (glr_bn_infer: no statistics pass, no workspace, buffers untouched), and
+`fused_stem` folds the stem's BatchNorm + ReLU into the max-pool (glr_bn_relu_maxpool3s2_infer).  Every other case
+(eval mode with a graph to record, NCHW, CPU tensors of the host-logic tests) is torch's own BatchNorm + add + relu -
+the same operator from the library, not a CPU fallback of the loss path.
+`GLR_FUSED_BN=0` switches all kernels off, `GLR_FUSED_BN_EVAL=0` the inference ones alone (A/B measurements)."""
 
 import os
 
@@ -17,6 +21,7 @@ import torch.nn.functional as F
 from .. import _native as N
 
 ENABLED = os.environ.get("GLR_FUSED_BN", "1") != "0"
+EVAL_ENABLED = os.environ.get("GLR_FUSED_BN_EVAL", "1") != "0"     # the eval-mode (inference) kernels; needs ENABLED too
 
 # (device index, stream) -> fp32 workspace for the partial sums.  A workspace is only ever touched by launches of ONE
 # stream, so stream order alone makes its reuse safe - also when the two encoders run on two streams.
@@ -87,17 +92,21 @@ class _BNAct(torch.autograd.Function):
         return dx, dres, out[0], out[1], None, None, None, None, None, None, None
 
 
-def _fusable(bn, x, residual):
+def _operands_ok(bn, x, residual):
+    """what the training and the inference kernels both ask of the module and the tensors"""
     c = x.shape[1] if x.dim() == 4 else 0
     # exactly nn.BatchNorm2d: SyncBatchNorm (Trainer(sync_bn=True)) has the same attributes but its statistics span the
     # process group - the per-rank kernels would silently turn the global-batch parity mode into per-rank BN
     return (type(bn) is torch.nn.BatchNorm2d and ENABLED and x.is_cuda and x.dtype in (torch.bfloat16, torch.float32) and x.dim() == 4
-            and bn.training and bn.affine
-            and bn.track_running_stats and bn.momentum is not None and 8 <= c <= 2048 and (c & (c - 1)) == 0
+            and bn.affine and bn.track_running_stats and 8 <= c <= 2048 and (c & (c - 1)) == 0
             and bn.weight.dtype == torch.float32 and bn.bias.dtype == torch.float32
             and x.is_contiguous(memory_format=torch.channels_last)
             and (residual is None or (residual.dtype == x.dtype and residual.shape == x.shape
                                       and residual.is_contiguous(memory_format=torch.channels_last))))
+
+
+def _fusable(bn, x, residual):
+    return bn.training and bn.momentum is not None and _operands_ok(bn, x, residual)
 
 
 class SkipPair:
@@ -109,14 +118,36 @@ class SkipPair:
         self.main, self.skip = main, skip
 
 
+def _infer_fusable(bn, x, residual):
+    """eval mode where autograd would record nothing: the one-launch inference kernels (glr_bn_infer) apply.  Eval mode
+    WITH a graph to build (grad enabled and x / residual / weight / bias requiring grad) stays torch's: there is no
+    backward for the running-statistics form."""
+    return (EVAL_ENABLED and not bn.training and _operands_ok(bn, x, residual)
+            and bn.running_mean.dtype == torch.float32 and bn.running_var.dtype == torch.float32
+            and (not torch.is_grad_enabled()
+                 or not (x.requires_grad or bn.weight.requires_grad or bn.bias.requires_grad
+                         or (residual is not None and residual.requires_grad))))
+
+
+def _bn_infer(bn, x, residual, relu):
+    n, c, h, w = x.shape
+    y = torch.empty_like(x)                                  # channels_last like x
+    N.check(N.lib().glr_bn_infer(N.ptr(x), N.ptr(residual), N.ptr(bn.weight), N.ptr(bn.bias), N.ptr(bn.running_mean),
+                                 N.ptr(bn.running_var), n * h * w, c, float(bn.eps), 1 if relu else 0, N.ptr(y),
+                                 N.dtype_code(x.dtype), N.stream()), "glr_bn_infer")
+    return y
+
+
 def fused_bn_act(bn, x, residual=None, relu=True, fork=False):
     """relu?(bn(x) (+ residual)) with nn.BatchNorm2d `bn`'s parameters and running statistics.  fork=True (fused path,
-    with a residual): returns a SkipPair instead of a tensor."""
+    with a residual, grad enabled): returns a SkipPair instead of a tensor."""
     if _fusable(bn, x, residual):
         fork = bool(fork and residual is not None and torch.is_grad_enabled())
         out = _BNAct.apply(x, residual, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.num_batches_tracked, bn.eps,
                            bn.momentum, relu, fork)
         return SkipPair(*out) if fork else out
+    if _infer_fusable(bn, x, residual):
+        return _bn_infer(bn, x, residual, relu)
     out = bn(x)
     if residual is not None:
         out = out + residual
@@ -146,12 +177,31 @@ class _MaxPool3s2(torch.autograd.Function):
         return dx
 
 
-def fused_maxpool(pool, x):
-    """nn.MaxPool2d(3, stride=2, padding=1) `pool` on x; channels-last bf16 on the GPU runs the one-byte-argmax kernels."""
+def _pool_fusable(pool, x):
     def _is(v, k):
         return v == k or v == (k, k)
-    if (ENABLED and x.is_cuda and x.dtype == torch.bfloat16 and x.dim() == 4 and x.shape[1] % 8 == 0
+    return (ENABLED and x.is_cuda and x.dtype == torch.bfloat16 and x.dim() == 4 and x.shape[1] % 8 == 0
             and x.is_contiguous(memory_format=torch.channels_last) and _is(pool.kernel_size, 3) and _is(pool.stride, 2)
-            and _is(pool.padding, 1) and _is(pool.dilation, 1) and not pool.ceil_mode and not pool.return_indices):
+            and _is(pool.padding, 1) and _is(pool.dilation, 1) and not pool.ceil_mode and not pool.return_indices)
+
+
+def fused_maxpool(pool, x):
+    """nn.MaxPool2d(3, stride=2, padding=1) `pool` on x; channels-last bf16 on the GPU runs the one-byte-argmax kernels."""
+    if _pool_fusable(pool, x):
         return _MaxPool3s2.apply(x)
     return pool(x)
+
+
+def fused_stem(bn, pool, x):
+    """pool(relu(bn(x))) of the ResNet stem on the conv1 output x.  Eval mode without autograd on channels-last bf16: ONE
+    launch (glr_bn_relu_maxpool3s2_infer; bitwise the two-kernel composition).  Otherwise exactly
+    fused_maxpool(pool, fused_bn_act(bn, x))."""
+    if _pool_fusable(pool, x) and _infer_fusable(bn, x, None):         # _pool_fusable: bf16 only, like the kernel
+        n, c, h, w = x.shape
+        y = torch.empty((n, c, (h - 1) // 2 + 1, (w - 1) // 2 + 1), dtype=x.dtype, device=x.device,
+                        memory_format=torch.channels_last)
+        N.check(N.lib().glr_bn_relu_maxpool3s2_infer(N.ptr(x), N.ptr(bn.weight), N.ptr(bn.bias), N.ptr(bn.running_mean),
+                                                     N.ptr(bn.running_var), n, h, w, c, float(bn.eps), N.ptr(y), N.stream()),
+                "glr_bn_relu_maxpool3s2_infer")
+        return y
+    return fused_maxpool(pool, fused_bn_act(bn, x))

@@ -384,6 +384,22 @@ int glr_bn_act_bwd(const void* x, const void* dy, const void* dy2, const void* y
                    const float* invstd, long long R, int C, int relu, int has_residual, float* workspace, float* out4c,
                    void* dx, void* dres, int dtype, void* stream);
 
+/* Eval-mode BatchNorm2d (+ residual add) (+ ReLU) without autograd: the same 53 sites when the image encoder runs under
+ * model.eval() and torch.no_grad() (Trainer.evaluate, get_similarities, zero-shot, retrieval).  ONE launch per site: no
+ * statistics, no workspace; nothing but y is written (the running buffers are inputs).  Per channel, in fp32,
+ *   sc = gamma / sqrt(run_var + eps),  sh = beta - run_mean sc,   y = relu?( fma(x, sc, sh) (+ residual) )
+ *   glr_bn_infer                 x / residual (NULL = none) / y: [R, C] like glr_bn_act_fwd, `dtype` GLR_BF16 or GLR_F32
+ *   glr_bn_relu_maxpool3s2_infer the stem: x bf16 [B, H, W, C] (the conv1 output), C % 8 == 0 -> y bf16 [B, Ho, Wo, C],
+ *                                Ho = (H - 1) / 2 + 1: MaxPool2d(3, stride 2, padding 1) of relu(fma(x, sc, sh)), maximum in
+ *                                fp32 and one rounding at the store; no argmax.  Bitwise equal to glr_maxpool3s2_fwd of
+ *                                glr_bn_infer(x, relu = 1) (rounding is monotone).
+ * HBM-bound: 2 (3) tensor passes per site; the stem reads E and writes E / 4.
+ */
+int glr_bn_infer(const void* x, const void* residual, const float* gamma, const float* beta, const float* run_mean,
+                 const float* run_var, long long R, int C, float eps, int relu, void* y, int dtype, void* stream);
+int glr_bn_relu_maxpool3s2_infer(const void* x, const float* gamma, const float* beta, const float* run_mean,
+                                 const float* run_var, int B, int H, int W, int C, float eps, void* y, void* stream);
+
 /* ------------------------------------------------------------------------------------------
  * Fused  y = LayerNorm(dropout(h) + inp)  of the BERT sub-layer outputs (reference: transformers'
  * BertSelfOutput / BertOutput inside the BertModel of gloria/models/text_model.py:18-20, run under native AMP).
