@@ -29,13 +29,15 @@ __global__ void __launch_bounds__(AT_NT) k_attn_fwd(AttnParams p) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l31 = lane & 31, h = lane >> 5;
   const int bh = blockIdx.x, b = bh / p.nh, hd = bh % p.nh;
-  const int L = p.L, tp = p.tp, lk = (L + 15) & ~15, kt = lk >> 4, nkb = (L + 31) >> 5;
+  int L; size_t row_base;
+  attn_rows(p, b, row_base, L);
+  const int tp = p.tp, lk = (L + 15) & ~15, kt = lk >> 4, nkb = (L + 31) >> 5;
   unsigned char* Qs = smem;
   unsigned char* Ks = Qs + 128 * AT_RP;
   unsigned char* Vt = Ks + 128 * AT_RP;
   unsigned char* Ps = smem;                      // the P slabs take the place of Q / K once every wave has its scores
   float* kb = reinterpret_cast<float*>(Vt + 64 * tp);
-  const size_t base = (size_t)b * L * p.ld + (size_t)hd * 64;
+  const size_t base = row_base * p.ld + (size_t)hd * 64;
   {
     uint4 rq[4], rk[4], rv[4];
     tile_load(p.q + base, p.ld, L, rq, tid);
@@ -106,7 +108,7 @@ __global__ void __launch_bounds__(AT_NT) k_attn_fwd(AttnParams p) {
   f32x16 out[2];
   zero16(out[0]); zero16(out[1]);
   gemm_tokens(out, slab, Vt, tp, kt, l31, h);
-  store_rows(out, slab, tp, p.o + (size_t)b * L * p.ld_o + (size_t)hd * 64, p.ld_o, row0, L, lane, l31, h);
+  store_rows(out, slab, tp, p.o + row_base * p.ld_o + (size_t)hd * 64, p.ld_o, row0, L, lane, l31, h);
 }
 
 // ---- backward, split by pass so that two workgroups fit a CU (56 / 72 KB of LDS instead of 155 KB in one kernel:
@@ -118,7 +120,9 @@ __global__ void __launch_bounds__(AT_NT, 2) k_attn_bwd_q(AttnParams p) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l31 = lane & 31, h = lane >> 5;
   const int bh = blockIdx.x, b = bh / p.nh, hd = bh % p.nh;
-  const int L = p.L, tp = p.tp, lk = (L + 15) & ~15, kt = lk >> 4, nkb = (L + 31) >> 5;
+  int L; size_t row_base;
+  attn_rows(p, b, row_base, L);
+  const int tp = p.tp, lk = (L + 15) & ~15, kt = lk >> 4, nkb = (L + 31) >> 5;
   unsigned char* Ks = smem;
   unsigned char* Vs = Ks + 128 * AT_RP;
   unsigned char* Kt = Vs + 128 * AT_RP;
@@ -127,7 +131,7 @@ __global__ void __launch_bounds__(AT_NT, 2) k_attn_bwd_q(AttnParams p) {
   float* lse = kb + 128;
   float* delta = lse + 128;                                       // [128], rows of wave w written by wave w
   unsigned* keep = reinterpret_cast<unsigned*>(delta + 128);      // [128][4]
-  const size_t base = (size_t)b * L * p.ld + (size_t)hd * 64, base_o = (size_t)b * L * p.ld_o + (size_t)hd * 64;
+  const size_t base = row_base * p.ld + (size_t)hd * 64, base_o = row_base * p.ld_o + (size_t)hd * 64;
   const bool drop = p.p_drop > 0.f;
   const int row0 = 32 * wave;
   const bool active = row0 < L;
@@ -196,7 +200,9 @@ __global__ void __launch_bounds__(AT_NT, 2) k_attn_bwd_kv(AttnParams p) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l31 = lane & 31, h = lane >> 5;
   const int bh = blockIdx.x, b = bh / p.nh, hd = bh % p.nh;
-  const int L = p.L, tp = p.tp, lk = (L + 15) & ~15, kt = lk >> 4, nkb = (L + 31) >> 5;
+  int L; size_t row_base;
+  attn_rows(p, b, row_base, L);
+  const int tp = p.tp, lk = (L + 15) & ~15, kt = lk >> 4, nkb = (L + 31) >> 5;
   unsigned char* Qs = smem;
   unsigned char* Gs = Qs + 128 * AT_RP;          // dO
   unsigned char* Qt = Gs + 128 * AT_RP;
@@ -206,7 +212,7 @@ __global__ void __launch_bounds__(AT_NT, 2) k_attn_bwd_kv(AttnParams p) {
   float* lse = kb + 128;
   float* delta = lse + 128;                                       // [2][128] partial sums (the two thread halves)
   unsigned* keep = reinterpret_cast<unsigned*>(delta + 256);      // [128][4]
-  const size_t base = (size_t)b * L * p.ld + (size_t)hd * 64, base_o = (size_t)b * L * p.ld_o + (size_t)hd * 64;
+  const size_t base = row_base * p.ld + (size_t)hd * 64, base_o = row_base * p.ld_o + (size_t)hd * 64;
   const bool drop = p.p_drop > 0.f;
   const int row0 = 32 * wave;
   const bool active = row0 < L;
@@ -294,6 +300,37 @@ extern "C" int glr_attn_max_tokens(int backward) {
   return 0;
 }
 
+// launches shared by the padded and the packed-rows entry points (p.L sizes the LDS: L, or the longest sentence)
+static int attn_launch_fwd(const AttnParams& p, void* stream) {
+  const int lds = (int)attn_lds_fwd(p.L);
+  static GlrLdsAttr lds_fwd;
+  if (glr_ensure_lds(lds_fwd, (const void*)k_attn_fwd, lds) != GLR_OK) return GLR_ELAUNCH;
+  hipLaunchKernelGGL(k_attn_fwd, dim3(p.B * p.nh), dim3(AT_NT), lds, (hipStream_t)stream, p);
+  GLR_CHECK_LAUNCH();
+  return GLR_OK;
+}
+static int attn_launch_bwd(const AttnParams& p, void* stream) {
+  const int lds_q = (int)attn_lds_bwd_q(p.L), lds_kv = (int)attn_lds_bwd_kv(p.L);
+  static GlrLdsAttr lds_bq, lds_bkv;
+  if (glr_ensure_lds(lds_bq, (const void*)k_attn_bwd_q, lds_q) != GLR_OK) return GLR_ELAUNCH;
+  if (glr_ensure_lds(lds_bkv, (const void*)k_attn_bwd_kv, lds_kv) != GLR_OK) return GLR_ELAUNCH;
+  hipLaunchKernelGGL(k_attn_bwd_q, dim3(p.B * p.nh), dim3(AT_NT), lds_q, (hipStream_t)stream, p);
+  GLR_CHECK_LAUNCH();
+  hipLaunchKernelGGL(k_attn_bwd_kv, dim3(p.B * p.nh), dim3(AT_NT), lds_kv, (hipStream_t)stream, p);
+  GLR_CHECK_LAUNCH();
+  return GLR_OK;
+}
+// longest sentence of a host row_start [B + 1], or 0 unless every sentence has 1 .. max_n rows
+static int attn_rows_longest(const int32_t* rs, int B, int max_n) {
+  int longest = 0;
+  for (int b = 0; b < B; ++b) {
+    const long long n = (long long)rs[b + 1] - rs[b];
+    if (rs[b] < 0 || n < 1 || n > max_n) return 0;
+    if ((int)n > longest) longest = (int)n;
+  }
+  return longest;
+}
+
 extern "C" int glr_attn_fwd(const void* q, const void* k, const void* v, const uint8_t* key_mask, int B, int n_heads, int L, int ld,
                             int ld_o, float scale, float p_drop, unsigned long long seed, unsigned long long offset,
                             const unsigned long long* rng_cell, void* o, float* lse, uint32_t* keep, void* stream) {
@@ -302,12 +339,7 @@ extern "C" int glr_attn_fwd(const void* q, const void* k, const void* v, const u
   if (rc != GLR_OK) return rc;
   if (!o || !lse || (p_drop > 0.f && !keep) || L > glr_attn_max_tokens(0)) return GLR_EINVAL;
   p.o = (unsigned short*)o; p.lse = lse; p.keep = keep; p.rng = rng_cell;
-  const int lds = (int)attn_lds_fwd(L);
-  static GlrLdsAttr lds_fwd;
-  if (glr_ensure_lds(lds_fwd, (const void*)k_attn_fwd, lds) != GLR_OK) return GLR_ELAUNCH;
-  hipLaunchKernelGGL(k_attn_fwd, dim3(B * n_heads), dim3(AT_NT), lds, (hipStream_t)stream, p);
-  GLR_CHECK_LAUNCH();
-  return GLR_OK;
+  return attn_launch_fwd(p, stream);
 }
 
 extern "C" int glr_attn_bwd(const void* q, const void* k, const void* v, const void* o, const void* d_o, const uint8_t* key_mask,
@@ -319,13 +351,36 @@ extern "C" int glr_attn_bwd(const void* q, const void* k, const void* v, const v
   if (!o || !d_o || !lse || !dq || !dk || !dv || (p_drop > 0.f && !keep) || L > glr_attn_max_tokens(1)) return GLR_EINVAL;
   p.o = (unsigned short*)const_cast<void*>(o); p.d_o = (const unsigned short*)d_o; p.lse = const_cast<float*>(lse);
   p.keep = const_cast<unsigned*>(keep); p.dq = (unsigned short*)dq; p.dk = (unsigned short*)dk; p.dv = (unsigned short*)dv;
-  const int lds_q = (int)attn_lds_bwd_q(L), lds_kv = (int)attn_lds_bwd_kv(L);
-  static GlrLdsAttr lds_bq, lds_bkv;
-  if (glr_ensure_lds(lds_bq, (const void*)k_attn_bwd_q, lds_q) != GLR_OK) return GLR_ELAUNCH;
-  if (glr_ensure_lds(lds_bkv, (const void*)k_attn_bwd_kv, lds_kv) != GLR_OK) return GLR_ELAUNCH;
-  hipLaunchKernelGGL(k_attn_bwd_q, dim3(B * n_heads), dim3(AT_NT), lds_q, (hipStream_t)stream, p);
-  GLR_CHECK_LAUNCH();
-  hipLaunchKernelGGL(k_attn_bwd_kv, dim3(B * n_heads), dim3(AT_NT), lds_kv, (hipStream_t)stream, p);
-  GLR_CHECK_LAUNCH();
-  return GLR_OK;
+  return attn_launch_bwd(p, stream);
+}
+
+extern "C" int glr_attn_rows_fwd(const void* q, const void* k, const void* v, const int32_t* row_start, const int32_t* row_start_host,
+                                 int B, int n_heads, int ld, int ld_o, float scale, float p_drop, unsigned long long seed,
+                                 unsigned long long offset, const unsigned long long* rng_cell, void* o, float* lse, uint32_t* keep,
+                                 void* stream) {
+  if (!row_start || !row_start_host || B <= 0) return GLR_EINVAL;
+  const int longest = attn_rows_longest(row_start_host, B, glr_attn_max_tokens(0));
+  if (longest == 0) return GLR_EINVAL;
+  AttnParams p;
+  const int rc = attn_fill(p, q, k, v, nullptr, B, n_heads, longest, ld, ld_o, scale, p_drop, seed, offset, 128);
+  if (rc != GLR_OK) return rc;
+  if (!o || !lse || (p_drop > 0.f && !keep)) return GLR_EINVAL;
+  p.o = (unsigned short*)o; p.lse = lse; p.keep = keep; p.rng = rng_cell; p.row_start = row_start;
+  return attn_launch_fwd(p, stream);
+}
+
+extern "C" int glr_attn_rows_bwd(const void* q, const void* k, const void* v, const void* o, const void* d_o, const int32_t* row_start,
+                                 const int32_t* row_start_host, const float* lse, const uint32_t* keep, int B, int n_heads, int ld,
+                                 int ld_o, float scale, float p_drop, void* dq, void* dk, void* dv, void* stream) {
+  if (!row_start || !row_start_host || B <= 0) return GLR_EINVAL;
+  const int longest = attn_rows_longest(row_start_host, B, glr_attn_max_tokens(1));
+  if (longest == 0) return GLR_EINVAL;
+  AttnParams p;
+  const int rc = attn_fill(p, q, k, v, nullptr, B, n_heads, longest, ld, ld_o, scale, p_drop, 0, 0, 128);
+  if (rc != GLR_OK) return rc;
+  if (!o || !d_o || !lse || !dq || !dk || !dv || (p_drop > 0.f && !keep)) return GLR_EINVAL;
+  p.o = (unsigned short*)const_cast<void*>(o); p.d_o = (const unsigned short*)d_o; p.lse = const_cast<float*>(lse);
+  p.keep = const_cast<unsigned*>(keep); p.dq = (unsigned short*)dq; p.dk = (unsigned short*)dk; p.dv = (unsigned short*)dv;
+  p.row_start = row_start;
+  return attn_launch_bwd(p, stream);
 }

@@ -23,7 +23,21 @@ struct AttnParams {
   const unsigned short* d_o;        // bwd
   unsigned short* dq; unsigned short* dk; unsigned short* dv;
   int tp;                           // bytes per row of a token-contiguous LDS operand: max(2 * ceil16(L) + 16, 144)
+  const int* row_start;             // NULL, or [B + 1]: sentence b = rows [row_start[b], row_start[b + 1]) of a packed [T, ld]
+                                    // tensor (no pad rows, no key mask); L is then the longest sentence of the batch
 };
+
+// first row and token count of sentence b: the padded [B, L, ld] layout, or the packed one through row_start (the count is
+// held to the host's maximum, which sized tp and the LDS)
+__device__ __forceinline__ void attn_rows(const AttnParams& p, int b, size_t& row_base, int& L) {
+  L = p.L;
+  row_base = (size_t)b * L;
+  if (p.row_start != nullptr) {
+    const int r0 = p.row_start[b], n = p.row_start[b + 1] - r0;
+    row_base = (size_t)r0;
+    L = n < p.L ? n : p.L;
+  }
+}
 
 // dropout bits: a counter-based hash (two rounds of a 32-bit multiply-xorshift mixer, keyed by seed and offset) of the
 // score's position - 16 bits per score.  (Philox4x32-10 cost 40 quarter-rate integer multiplies per 8 scores here.)
@@ -182,7 +196,7 @@ inline int attn_fill(AttnParams& p, const void* q, const void* k, const void* v,
   p.q = (const unsigned short*)q; p.k = (const unsigned short*)k; p.v = (const unsigned short*)v; p.key_mask = key_mask;
   p.B = B; p.nh = nh; p.L = L; p.ld = ld; p.ld_o = ld_o; p.scale = scale; p.p_drop = p_drop;
   p.seed_lo = (unsigned)seed; p.seed_hi = (unsigned)(seed >> 32); p.off_lo = (unsigned)offset; p.off_hi = (unsigned)(offset >> 32);
-  p.rng = nullptr;
+  p.rng = nullptr; p.row_start = nullptr;
   p.o = nullptr; p.lse = nullptr; p.keep = nullptr; p.d_o = nullptr; p.dq = p.dk = p.dv = nullptr;
   p.tp = attn_tp(L < 128 ? L : 128);
   return GLR_OK;

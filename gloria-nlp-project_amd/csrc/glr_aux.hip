@@ -20,9 +20,12 @@ struct LayerPtrs {
 
 // grid (ceil(D/64), B), 256 threads = 64 features x 4 token phases; features past D are masked (any D).
 // dst[b][t] = word slot of token t (monotone non-decreasing over the kept tokens) or -1.
+// row_start (NULL = hidden states are [B, L, D]): the hidden states are packed [T, D], token t of sentence b is row
+// row_start[b] + t for t < row_start[b + 1] - row_start[b]; the tokens behind it do not exist (their dst must be -1).
 __global__ void __launch_bounds__(256) k_segsum_fwd(LayerPtrs hp, int n_layers, int in_dtype,
-                                                    const int* __restrict__ dst, float* __restrict__ word_emb,
-                                                    float* __restrict__ sent_emb, int L, int D, float layer_scale) {
+                                                    const int* __restrict__ dst, const int* __restrict__ row_start,
+                                                    float* __restrict__ word_emb, float* __restrict__ sent_emb, int L, int D,
+                                                    float layer_scale) {
   extern __shared__ float tile[];                 // [64][L + 1]  word slots of 64 features
   const int b = blockIdx.y, d0 = blockIdx.x * 64;
   const int dx = threadIdx.x & 63, ph = threadIdx.x >> 6;
@@ -32,11 +35,13 @@ __global__ void __launch_bounds__(256) k_segsum_fwd(LayerPtrs hp, int n_layers, 
   // one thread per feature walks the tokens in order (fixed summation order => bitwise reproducible);
   // the other three quarter-blocks only help with zeroing and the transposed write-out
   if (ph == 0 && d0 + dx < D) {
-    for (int t = 0; t < L; ++t) {
+    const size_t row0 = row_start ? (size_t)row_start[b] : (size_t)b * L;
+    const int nt = row_start ? min(row_start[b + 1] - row_start[b], L) : L;
+    for (int t = 0; t < nt; ++t) {
       const int slot = dst[(size_t)b * L + t];
       if (slot < 0) continue;
       float v = 0.f;
-      for (int l = 0; l < n_layers; ++l) v += ld_any(hp.h[l], ((size_t)b * L + t) * D + d0 + dx, in_dtype);
+      for (int l = 0; l < n_layers; ++l) v += ld_any(hp.h[l], (row0 + t) * D + d0 + dx, in_dtype);
       tile[dx * LP + slot] += v * layer_scale;
     }
   }
@@ -55,8 +60,9 @@ __global__ void __launch_bounds__(256) k_segsum_fwd(LayerPtrs hp, int n_layers, 
 
 // d_hidden[b][t][d] (same for every layer) = layer_scale * (d_word[b][d][dst] + d_sent[b][d] / L) if dst >= 0
 __global__ void __launch_bounds__(256) k_segsum_bwd(const float* __restrict__ d_word, const float* __restrict__ d_sent,
-                                                    const int* __restrict__ dst, void* __restrict__ d_hidden,
-                                                    int out_dtype, int L, int D, float layer_scale) {
+                                                    const int* __restrict__ dst, const int* __restrict__ row_start,
+                                                    void* __restrict__ d_hidden, int out_dtype, int L, int D,
+                                                    float layer_scale) {
   extern __shared__ float tile[];                 // [64][L + 1]
   const int b = blockIdx.y, d0 = blockIdx.x * 64;
   const int dx = threadIdx.x & 63, ph = threadIdx.x >> 6;
@@ -68,10 +74,12 @@ __global__ void __launch_bounds__(256) k_segsum_bwd(const float* __restrict__ d_
   __syncthreads();
   if (d0 + dx >= D) return;
   const float gs = d_sent ? d_sent[(size_t)b * D + d0 + dx] / (float)L : 0.f;
-  for (int t = ph; t < L; t += 4) {
+  const size_t row0 = row_start ? (size_t)row_start[b] : (size_t)b * L;
+  const int nt = row_start ? min(row_start[b + 1] - row_start[b], L) : L;
+  for (int t = ph; t < nt; t += 4) {
     const int slot = dst[(size_t)b * L + t];
     const float v = slot >= 0 ? (tile[dx * LP + slot] + gs) * layer_scale : 0.f;
-    st_any(d_hidden, ((size_t)b * L + t) * D + d0 + dx, out_dtype, v);
+    st_any(d_hidden, (row0 + t) * D + d0 + dx, out_dtype, v);
   }
 }
 
@@ -448,9 +456,8 @@ extern "C" int glr_attn_reg_bwd(const float* amean, int B_img, int n_sent, int S
   return GLR_OK;
 }
 
-extern "C" int glr_wordpiece_segsum_fwd(const void* const* hidden, int n_layers, int in_dtype, const int32_t* dst,
-                                        float* word_emb, float* sent_emb, int B, int L, int D, int mean_layers,
-                                        void* stream) {
+static int segsum_fwd(const void* const* hidden, int n_layers, int in_dtype, const int32_t* dst, const int32_t* row_start,
+                      float* word_emb, float* sent_emb, int B, int L, int D, int mean_layers, void* stream) {
   if (!hidden || !dst || !word_emb || !sent_emb || n_layers < 1 || n_layers > K5_MAX_LAYERS || B <= 0 || L <= 0 || D <= 0)
     return GLR_EINVAL;
   if (in_dtype != GLR_F32 && in_dtype != GLR_BF16) return GLR_EDTYPE;
@@ -460,22 +467,47 @@ extern "C" int glr_wordpiece_segsum_fwd(const void* const* hidden, int n_layers,
   const size_t lds = (size_t)64 * (L + 1) * sizeof(float);
   if (lds > 64 * 1024) return GLR_EINVAL;
   hipLaunchKernelGGL(k_segsum_fwd, dim3((D + 63) / 64, B), dim3(256), lds, (hipStream_t)stream, hp, n_layers, in_dtype, dst,
-                     word_emb, sent_emb, L, D, mean_layers ? 1.f / (float)n_layers : 1.f);
+                     row_start, word_emb, sent_emb, L, D, mean_layers ? 1.f / (float)n_layers : 1.f);
   GLR_CHECK_LAUNCH();
   return GLR_OK;
+}
+
+static int segsum_bwd(const float* d_word, const float* d_sent, const int32_t* dst, const int32_t* row_start, void* d_hidden,
+                      int out_dtype, int B, int L, int D, int n_layers, int mean_layers, void* stream) {
+  if (!dst || !d_hidden || B <= 0 || L <= 0 || D <= 0 || n_layers < 1) return GLR_EINVAL;
+  if (out_dtype != GLR_F32 && out_dtype != GLR_BF16) return GLR_EDTYPE;
+  const size_t lds = (size_t)64 * (L + 1) * sizeof(float);
+  if (lds > 64 * 1024) return GLR_EINVAL;
+  hipLaunchKernelGGL(k_segsum_bwd, dim3((D + 63) / 64, B), dim3(256), lds, (hipStream_t)stream, d_word, d_sent, dst, row_start,
+                     d_hidden, out_dtype, L, D, mean_layers ? 1.f / (float)n_layers : 1.f);
+  GLR_CHECK_LAUNCH();
+  return GLR_OK;
+}
+
+extern "C" int glr_wordpiece_segsum_fwd(const void* const* hidden, int n_layers, int in_dtype, const int32_t* dst,
+                                        float* word_emb, float* sent_emb, int B, int L, int D, int mean_layers,
+                                        void* stream) {
+  return segsum_fwd(hidden, n_layers, in_dtype, dst, nullptr, word_emb, sent_emb, B, L, D, mean_layers, stream);
 }
 
 extern "C" int glr_wordpiece_segsum_bwd(const float* d_word, const float* d_sent, const int32_t* dst, void* d_hidden,
                                         int out_dtype, int B, int L, int D, int n_layers, int mean_layers,
                                         void* stream) {
-  if (!dst || !d_hidden || B <= 0 || L <= 0 || D <= 0 || n_layers < 1) return GLR_EINVAL;
-  if (out_dtype != GLR_F32 && out_dtype != GLR_BF16) return GLR_EDTYPE;
-  const size_t lds = (size_t)64 * (L + 1) * sizeof(float);
-  if (lds > 64 * 1024) return GLR_EINVAL;
-  hipLaunchKernelGGL(k_segsum_bwd, dim3((D + 63) / 64, B), dim3(256), lds, (hipStream_t)stream, d_word, d_sent, dst, d_hidden,
-                     out_dtype, L, D, mean_layers ? 1.f / (float)n_layers : 1.f);
-  GLR_CHECK_LAUNCH();
-  return GLR_OK;
+  return segsum_bwd(d_word, d_sent, dst, nullptr, d_hidden, out_dtype, B, L, D, n_layers, mean_layers, stream);
+}
+
+extern "C" int glr_wordpiece_segsum_rows_fwd(const void* const* hidden, int n_layers, int in_dtype, const int32_t* dst,
+                                             const int32_t* row_start, float* word_emb, float* sent_emb, int B, int L, int D,
+                                             int mean_layers, void* stream) {
+  if (!row_start) return GLR_EINVAL;
+  return segsum_fwd(hidden, n_layers, in_dtype, dst, row_start, word_emb, sent_emb, B, L, D, mean_layers, stream);
+}
+
+extern "C" int glr_wordpiece_segsum_rows_bwd(const float* d_word, const float* d_sent, const int32_t* dst, const int32_t* row_start,
+                                             void* d_hidden, int out_dtype, int B, int L, int D, int n_layers, int mean_layers,
+                                             void* stream) {
+  if (!row_start) return GLR_EINVAL;
+  return segsum_bwd(d_word, d_sent, dst, row_start, d_hidden, out_dtype, B, L, D, n_layers, mean_layers, stream);
 }
 
 extern "C" int glr_attn_sup_fwd(const float* attn, const int64_t* attn_off, const int32_t* cap_lens, int img_offset,

@@ -50,7 +50,8 @@ __global__ void __launch_bounds__(LN_NT) k_drop_add_ln_fwd(const unsigned short*
                                                            long long R, float eps, float p_drop, unsigned seed_lo, unsigned seed_hi,
                                                            unsigned off_lo, unsigned off_hi, const unsigned long long* __restrict__ rng,
                                                            float* __restrict__ out32, unsigned short* __restrict__ out16,
-                                                           float* __restrict__ stats, unsigned long long* __restrict__ mask) {
+                                                           float* __restrict__ stats, unsigned long long* __restrict__ mask,
+                                                           const int* __restrict__ row_ids) {
   constexpr int H = NQ * 256;
   const int lane = threadIdx.x & 63;
   const long long row = (long long)blockIdx.x * (LN_NT / 64) + (threadIdx.x >> 6);
@@ -64,6 +65,8 @@ __global__ void __launch_bounds__(LN_NT) k_drop_add_ln_fwd(const unsigned short*
   const float inv_keep = drop ? 1.f / (1.f - p_drop) : 1.f;
   float z[NQ][4];
   unsigned long long myword = 0ull;
+  // packed rows draw the bits of the row they were gathered from (row_ids[row] of the padded tensor)
+  const unsigned long long ctr_row = row_ids != nullptr ? (unsigned long long)(unsigned)row_ids[row] : (unsigned long long)row;
 #pragma unroll
   for (int i = 0; i < NQ; ++i) {
     const int quad = lane + 64 * i;
@@ -72,7 +75,7 @@ __global__ void __launch_bounds__(LN_NT) k_drop_add_ln_fwd(const unsigned short*
     const float4 iv = *reinterpret_cast<const float4*>(inp + row * H + 4 * quad);
     const float ivv[4] = {iv.x, iv.y, iv.z, iv.w};
     if (drop) {
-      const unsigned long long ctr = (unsigned long long)row * (H / 4) + quad;
+      const unsigned long long ctr = ctr_row * (H / 4) + quad;
       const U4 rnd = philox4x32((unsigned)ctr, (unsigned)(ctr >> 32), off_lo, off_hi, seed_lo, seed_hi);
       const unsigned rr[4] = {rnd.x, rnd.y, rnd.z, rnd.w};
 #pragma unroll
@@ -328,17 +331,17 @@ extern "C" int glr_colsum_bf16(const void* x16, long long R, int C, float* works
   return GLR_OK;
 }
 
-extern "C" int glr_drop_add_ln_fwd(const void* h16, const float* inp32, const float* gamma, const float* beta, long long R, int H,
+static int drop_add_ln_fwd(const void* h16, const float* inp32, const float* gamma, const float* beta, long long R, int H,
                                    float eps, float p_drop, unsigned long long seed, unsigned long long offset,
                                    const unsigned long long* rng_cell, float* out32, void* out16, float* stats,
-                                   unsigned long long* mask, void* stream) {
+                                   unsigned long long* mask, const int32_t* row_ids, void* stream) {
   if (!h16 || !inp32 || !gamma || !beta || !out32 || !out16 || !stats || !ln_shape_ok(R, H)) return GLR_EINVAL;
   if (p_drop < 0.f || p_drop >= 1.f || (p_drop > 0.f && !mask)) return GLR_EINVAL;
   hipStream_t st = (hipStream_t)stream;
   const int grid = (int)((R + LN_NT / 64 - 1) / (LN_NT / 64));
 #define GLR_LN_FWD(NQ)                                                                                                      \
   hipLaunchKernelGGL((k_drop_add_ln_fwd<NQ>), dim3(grid), dim3(LN_NT), 0, st, (const unsigned short*)h16, inp32, gamma, beta, R, \
-                     eps, p_drop, (unsigned)seed, (unsigned)(seed >> 32), (unsigned)offset, (unsigned)(offset >> 32), rng_cell, out32, (unsigned short*)out16, stats, mask)
+                     eps, p_drop, (unsigned)seed, (unsigned)(seed >> 32), (unsigned)offset, (unsigned)(offset >> 32), rng_cell, out32, (unsigned short*)out16, stats, mask, row_ids)
   switch (H / 256) {
     case 1: GLR_LN_FWD(1); break;
     case 2: GLR_LN_FWD(2); break;
@@ -348,6 +351,21 @@ extern "C" int glr_drop_add_ln_fwd(const void* h16, const float* inp32, const fl
 #undef GLR_LN_FWD
   GLR_CHECK_LAUNCH();
   return GLR_OK;
+}
+
+extern "C" int glr_drop_add_ln_fwd(const void* h16, const float* inp32, const float* gamma, const float* beta, long long R, int H,
+                                   float eps, float p_drop, unsigned long long seed, unsigned long long offset,
+                                   const unsigned long long* rng_cell, float* out32, void* out16, float* stats,
+                                   unsigned long long* mask, void* stream) {
+  return drop_add_ln_fwd(h16, inp32, gamma, beta, R, H, eps, p_drop, seed, offset, rng_cell, out32, out16, stats, mask, nullptr, stream);
+}
+
+extern "C" int glr_drop_add_ln_rows_fwd(const void* h16, const float* inp32, const float* gamma, const float* beta,
+                                        const int32_t* row_ids, long long R, int H, float eps, float p_drop, unsigned long long seed,
+                                        unsigned long long offset, const unsigned long long* rng_cell, float* out32, void* out16,
+                                        float* stats, unsigned long long* mask, void* stream) {
+  if (!row_ids) return GLR_EINVAL;
+  return drop_add_ln_fwd(h16, inp32, gamma, beta, R, H, eps, p_drop, seed, offset, rng_cell, out32, out16, stats, mask, row_ids, stream);
 }
 
 extern "C" int glr_drop_add_ln_bwd(const float* dy32, const void* dy16, const void* h16, const float* inp32, const float* gamma,

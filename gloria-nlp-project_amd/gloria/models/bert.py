@@ -8,10 +8,11 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from .fused_attn import packed_fusable, self_attention, self_attention_packed
+from .fused_attn import packed_fusable, self_attention, self_attention_packed, self_attention_rows
 from .fused_embed import type_embedding, word_embedding
 from .fused_linear import linear
 from .fused_ln import dense_drop_add_ln
+from .text_rows import PackedRows
 
 
 class BertConfig:
@@ -48,6 +49,11 @@ class BertEmbeddings(nn.Module):
         return self.dropout(self.LayerNorm(x))
 
 
+def _row_ids(bias):
+    """the layers take a PackedRows in place of the key mask when they run on real token rows only"""
+    return bias.row_ids if isinstance(bias, PackedRows) else None
+
+
 class BertSelfAttention(nn.Module):
     def __init__(self, c):
         super().__init__()
@@ -60,6 +66,11 @@ class BertSelfAttention(nn.Module):
     def forward(self, x, bias):
         # bias: bool key mask [B, 1, 1, L] (True = attend) or None.  softmax(QK^T) -> dropout -> .V on the Linear outputs
         # as they are: one HIP kernel per direction for short captions under bf16 autocast (models/fused_attn.py)
+        if isinstance(bias, PackedRows):
+            # x: [T, H], the real token rows only (models/text_rows.py); every key of a sentence is live
+            w = torch.cat([self.query.weight, self.key.weight, self.value.weight], 0)
+            b_ = torch.cat([self.query.bias, self.key.bias, self.value.bias], 0)
+            return self_attention_rows(linear(x, w, b_), bias, self.nh, self.p, self.training)
         B, L, H = x.shape
         key_mask = None if bias is None else bias.reshape(B, L)
         if packed_fusable(x, self.nh, H, L, key_mask):
@@ -78,9 +89,10 @@ class BertSelfOutput(nn.Module):
         self.LayerNorm = nn.LayerNorm(c.hidden_size, eps=c.layer_norm_eps)
         self.dropout = nn.Dropout(c.hidden_dropout_prob)
 
-    def forward(self, h, inp):
+    def forward(self, h, inp, row_ids=None):
         # (y fp32, y bf16 | None): dropout + residual + LayerNorm in one HIP pass under bf16 autocast (models/fused_ln.py)
-        return dense_drop_add_ln(self.dense, h, inp, self.LayerNorm, self.dropout.p, self.training)
+        # row_ids: the padded rows these packed rows came from (their dropout bits), models/text_rows.py
+        return dense_drop_add_ln(self.dense, h, inp, self.LayerNorm, self.dropout.p, self.training, row_ids)
 
 
 class BertAttention(nn.Module):
@@ -91,7 +103,7 @@ class BertAttention(nn.Module):
 
     def forward(self, x, bias, x16=None):
         # x16: the bf16 copy of x the fused sub-layer epilogue already wrote (the operand autocast would cast x to)
-        return self.output(self.self(x if x16 is None else x16, bias), x)
+        return self.output(self.self(x if x16 is None else x16, bias), x, _row_ids(bias))
 
 
 class BertIntermediate(nn.Module):
@@ -110,8 +122,8 @@ class BertOutput(nn.Module):
         self.LayerNorm = nn.LayerNorm(c.hidden_size, eps=c.layer_norm_eps)
         self.dropout = nn.Dropout(c.hidden_dropout_prob)
 
-    def forward(self, h, inp):
-        return dense_drop_add_ln(self.dense, h, inp, self.LayerNorm, self.dropout.p, self.training)
+    def forward(self, h, inp, row_ids=None):
+        return dense_drop_add_ln(self.dense, h, inp, self.LayerNorm, self.dropout.p, self.training, row_ids)
 
 
 class BertLayer(nn.Module):
@@ -124,7 +136,7 @@ class BertLayer(nn.Module):
     def forward(self, x, bias, x16=None):
         """(hidden state fp32, its bf16 copy or None)"""
         a, a16 = self.attention(x, bias, x16)
-        return self.output(self.intermediate(a if a16 is None else a16), a)
+        return self.output(self.intermediate(a if a16 is None else a16), a, _row_ids(bias))
 
 
 class BertEncoderStack(nn.Module):
@@ -149,6 +161,18 @@ class BertStackPath(nn.Module):
             x, x16 = layer(x, key_mask4, x16)
             hidden.append(x)
         return tuple(hidden[-self.n_out:])
+
+
+def encode_rows(encoder, x, rows, n_out):
+    """The encoder layers on the real token rows only: (embedding output [B, L, H], PackedRows) -> the last n_out hidden
+    states (the gathered embedding output counts as the first, as in BertModel.forward) as [T, H].  One gather in front;
+    autograd scatters the gradient back to the padded embedding output."""
+    x = x.reshape(rows.B * rows.L, x.shape[-1]).index_select(0, rows.row_ids64)
+    hidden, x16 = [x], None
+    for layer in encoder.layer:
+        x, x16 = layer(x, rows, x16)
+        hidden.append(x)
+    return tuple(hidden[-int(n_out):])
 
 
 class BertPooler(nn.Module):

@@ -127,6 +127,54 @@ class _SelfAttnPacked(torch.autograd.Function):
         return dqkv, None, None, None, None
 
 
+class _SelfAttnRows(torch.autograd.Function):
+    """the short kernels on a packed [T, 3H] query|key|value tensor of real token rows only (models/text_rows.py):
+    sentence b owns rows row_start[b] .. row_start[b + 1], every key is live.  lse / keep keep the padded shapes and the
+    dropout counter its padded form, so a sentence draws the bits the padded kernel draws for it."""
+
+    @staticmethod
+    def forward(ctx, qkv, rows, nh, p, scale):
+        T, H3 = qkv.shape
+        H = H3 // 3
+        dev = qkv.device
+        o = torch.empty(T, H, dtype=qkv.dtype, device=dev)
+        lse = torch.empty(rows.B * nh, 128, dtype=torch.float32, device=dev)
+        keep = torch.empty(rows.B * nh, 128, 4, dtype=torch.int32, device=dev) if p > 0 else None
+        seed, off, cell = philox_args(dev) if p > 0 else (0, 0, None)
+        base = qkv.data_ptr()
+        N.check(N.lib().glr_attn_rows_fwd(N.c_void_p(base), N.c_void_p(base + 2 * H), N.c_void_p(base + 4 * H),
+                                          N.ptr(rows.row_start), rows.row_start_host.ctypes.data, rows.B, nh, H3, H,
+                                          float(scale), float(p), seed, off, cell, N.ptr(o), N.ptr(lse), N.ptr(keep),
+                                          N.stream()), "glr_attn_rows_fwd")
+        ctx.save_for_backward(qkv, o, lse, keep)
+        ctx.rows = rows
+        ctx.meta = (nh, float(p), float(scale))
+        return o
+
+    @staticmethod
+    def backward(ctx, d_o):
+        qkv, o, lse, keep = ctx.saved_tensors
+        rows = ctx.rows
+        nh, p, scale = ctx.meta
+        H = qkv.shape[1] // 3
+        d_o = d_o.to(torch.bfloat16).contiguous()
+        dqkv = torch.empty_like(qkv)
+        base, dbase = qkv.data_ptr(), dqkv.data_ptr()
+        N.check(N.lib().glr_attn_rows_bwd(N.c_void_p(base), N.c_void_p(base + 2 * H), N.c_void_p(base + 4 * H), N.ptr(o),
+                                          N.ptr(d_o), N.ptr(rows.row_start), rows.row_start_host.ctypes.data, N.ptr(lse),
+                                          N.ptr(keep), rows.B, nh, 3 * H, H, scale, p, N.c_void_p(dbase),
+                                          N.c_void_p(dbase + 2 * H), N.c_void_p(dbase + 4 * H), N.stream()),
+                "glr_attn_rows_bwd")
+        return dqkv, None, None, None, None
+
+
+def self_attention_rows(qkv, rows, nh, p, training):
+    """qkv: bf16 [T, 3H] (query | key | value columns) of the packed rows of `rows` -> context [T, H]"""
+    if qkv.dtype != torch.bfloat16 or qkv.shape[0] != rows.T or qkv.shape[1] != 3 * nh * 64:
+        raise RuntimeError("self_attention_rows: a bf16 [T, 3 * n_heads * 64] tensor of the plan's rows is required")
+    return _SelfAttnRows.apply(qkv.contiguous(), rows, nh, p if training else 0.0, 1.0 / 8.0)
+
+
 def _fusable(q, k, v, key_mask, nh):
     B, L, H = q.shape
     return (ENABLED and q.is_cuda and q.dtype == k.dtype == v.dtype == torch.bfloat16 and H == nh * 64 and _length_ok(L)

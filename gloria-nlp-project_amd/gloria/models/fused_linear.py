@@ -27,6 +27,8 @@ _WS_FLOATS = {}
 def _workspace(dev, R, C):
     n = _WS_FLOATS.get((R, C))
     if n is None:
+        if len(_WS_FLOATS) >= 64:        # the packed text route changes R every step: the cache stays small
+            _WS_FLOATS.clear()
         n = _WS_FLOATS[(R, C)] = int(N.lib().glr_colsum_workspace_floats(R, C))
     if n == 0:
         return None

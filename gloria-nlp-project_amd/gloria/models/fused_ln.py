@@ -29,6 +29,8 @@ _WS_FLOATS = {}
 def _workspace(dev, R, H):
     n = _WS_FLOATS.get((R, H))
     if n is None:
+        if len(_WS_FLOATS) >= 64:        # the packed text route changes R every step: the cache stays small
+            _WS_FLOATS.clear()
         n = _WS_FLOATS[(R, H)] = int(N.lib().glr_ln_workspace_floats(R, H))
     if torch.cuda.is_current_stream_capturing():        # a graph keeps its own: the shared one may be replaced later
         return torch.empty(n, dtype=torch.float32, device=dev)
@@ -42,9 +44,11 @@ def _workspace(dev, R, H):
 
 class _DropAddLN(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, h, inp, weight, bias, eps, p, h_bias=None):
+    def forward(ctx, h, inp, weight, bias, eps, p, h_bias=None, row_ids=None):
         # h_bias: the bias of the Linear that produced h, handed in only to RECEIVE its gradient (column sums of d_h,
         # accumulated by the backward kernel on its way) - see fused_linear.linear(..., bias_grad_from_epilogue=True)
+        # row_ids: int32 [R], the rows of the padded tensor these R rows were gathered from (models/text_rows.py): the
+        # dropout counter follows them, so a row's mask is the one the padded call draws for it
         L = N.lib()
         H = h.shape[-1]
         R = h.numel() // H
@@ -54,8 +58,15 @@ class _DropAddLN(torch.autograd.Function):
         stats = torch.empty(R, 2, dtype=torch.float32, device=dev)
         mask = torch.empty(R, H // 64, dtype=torch.int64, device=dev) if p > 0 else None
         seed, off, cell = philox_args(dev) if p > 0 else (0, 0, None)
-        N.check(L.glr_drop_add_ln_fwd(N.ptr(h), N.ptr(inp), N.ptr(weight), N.ptr(bias), R, H, float(eps), float(p), seed, off,
-                                      cell, N.ptr(out32), N.ptr(out16), N.ptr(stats), N.ptr(mask), N.stream()), "glr_drop_add_ln_fwd")
+        if row_ids is None:
+            N.check(L.glr_drop_add_ln_fwd(N.ptr(h), N.ptr(inp), N.ptr(weight), N.ptr(bias), R, H, float(eps), float(p), seed, off,
+                                          cell, N.ptr(out32), N.ptr(out16), N.ptr(stats), N.ptr(mask), N.stream()), "glr_drop_add_ln_fwd")
+        else:
+            if row_ids.dtype != torch.int32 or row_ids.numel() != R or not row_ids.is_contiguous():
+                raise RuntimeError("drop_add_ln: row_ids must be a contiguous int32 vector with one entry per row")
+            N.check(L.glr_drop_add_ln_rows_fwd(N.ptr(h), N.ptr(inp), N.ptr(weight), N.ptr(bias), N.ptr(row_ids), R, H, float(eps),
+                                               float(p), seed, off, cell, N.ptr(out32), N.ptr(out16), N.ptr(stats), N.ptr(mask),
+                                               N.stream()), "glr_drop_add_ln_rows_fwd")
         ctx.save_for_backward(h, inp, weight, stats, mask)
         ctx.p = float(p)
         ctx.hb = None if h_bias is None else (h_bias.dtype, h_bias.shape)
@@ -70,7 +81,7 @@ class _DropAddLN(torch.autograd.Function):
         R = h.numel() // H
         dev = h.device
         if d32 is None and d16 is None:
-            return None, None, None, None, None, None, None
+            return None, None, None, None, None, None, None, None
         if d32 is not None:
             d32 = d32.float().contiguous()
         if d16 is not None:
@@ -88,7 +99,7 @@ class _DropAddLN(torch.autograd.Function):
                                       ctx.p, N.ptr(d_inp), N.ptr(d_h), N.ptr(ws), N.ptr(dgb), c_off(dgb, H), N.ptr(dhb),
                                       int(dhb is not None and dhb.dtype == torch.bfloat16), N.stream()),
                 "glr_drop_add_ln_bwd")
-        return d_h, d_inp, dgb[0], dgb[1], None, None, dhb
+        return d_h, d_inp, dgb[0], dgb[1], None, None, dhb, None
 
 
 def c_off(t, n_elems):
@@ -104,17 +115,17 @@ def _fusable(h, inp, ln):
             and h.is_contiguous() and inp.is_contiguous())
 
 
-def drop_add_ln(h, inp, ln, p, training, h_bias=None):
+def drop_add_ln(h, inp, ln, p, training, h_bias=None, row_ids=None):
     """(LayerNorm(dropout(h) + inp) in fp32, the same rounded to bf16 or None).  h_bias: see _DropAddLN.forward - only
     pass it when `fusable(h, inp, ln)` (the unfused path has no gradient to give it)."""
     if _fusable(h, inp, ln):
-        return _DropAddLN.apply(h, inp, ln.weight, ln.bias, ln.eps, p if training else 0.0, h_bias)
+        return _DropAddLN.apply(h, inp, ln.weight, ln.bias, ln.eps, p if training else 0.0, h_bias, row_ids)
     if h_bias is not None:
         raise RuntimeError("drop_add_ln: h_bias given on the unfused path")
     return ln(F.dropout(h, p, training) + inp), None
 
 
-def dense_drop_add_ln(dense, x, inp, ln, p, training):
+def dense_drop_add_ln(dense, x, inp, ln, p, training, row_ids=None):
     """drop_add_ln(dense(x), inp, ...) of a BERT sub-layer output.  On the fused path under the bf16 flat optimizer the
     Linear's backward skips its bias gradient and the LayerNorm backward kernel supplies it (one pass over d_h less)."""
     from .fused_linear import linear, linear_fusable
@@ -124,5 +135,5 @@ def dense_drop_add_ln(dense, x, inp, ln, p, training):
             and ln.bias is not None and ln.bias.dtype == torch.float32 and tuple(ln.normalized_shape) == (H,)
             and inp.is_contiguous() and inp.shape[:-1] == x.shape[:-1] and inp.shape[-1] == H):
         h = linear(x, dense.weight, dense.bias, bias_grad_from_epilogue=True)
-        return _DropAddLN.apply(h, inp, ln.weight, ln.bias, ln.eps, p if training else 0.0, dense.bias)
-    return drop_add_ln(dense(x), inp, ln, p, training)
+        return _DropAddLN.apply(h, inp, ln.weight, ln.bias, ln.eps, p if training else 0.0, dense.bias, row_ids)
+    return drop_add_ln(dense(x), inp, ln, p, training, row_ids=row_ids)

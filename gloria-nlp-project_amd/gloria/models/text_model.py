@@ -20,7 +20,8 @@ import torch
 import torch.nn as nn
 
 from .. import _native as N
-from .bert import BertConfig, BertModel
+from . import text_rows
+from .bert import BertConfig, BertModel, encode_rows
 
 PAD, UNK, CLS, SEP, MASK = 0, 100, 101, 102, 103
 
@@ -160,6 +161,48 @@ class WordpieceSegSumFn(torch.autograd.Function):
         return (None, None) + tuple(dh.to(dt) for dt in dts)
 
 
+class WordpieceSegSumRowsFn(torch.autograd.Function):
+    """K5 on packed hidden states [T, D] (models/text_rows.py): token t of sentence b is row row_start[b] + t.  dst stays
+    [B, L], so word_emb / sent_emb are bitwise what the padded K5 gives; the backward writes the T packed rows."""
+
+    @staticmethod
+    def forward(ctx, dst, rows, mean_layers, *layers):
+        import ctypes
+        hs = [h.detach().contiguous() for h in layers]
+        if hs[0].dtype not in (torch.float32, torch.bfloat16):
+            hs = [h.float() for h in hs]
+        T, D = hs[0].shape
+        B, L = rows.B, rows.L
+        if T != rows.T or tuple(dst.shape) != (B, L):
+            raise RuntimeError("WordpieceSegSumRowsFn: hidden states and dst do not match the row plan")
+        dev = hs[0].device
+        word = torch.empty(B, D, L, dtype=torch.float32, device=dev)
+        sent = torch.empty(B, D, dtype=torch.float32, device=dev)
+        ptrs = (ctypes.c_void_p * len(hs))(*[h.data_ptr() for h in hs])
+        N.check(N.lib().glr_wordpiece_segsum_rows_fwd(ptrs, len(hs), N.dtype_code(hs[0].dtype), N.ptr(dst), N.ptr(rows.row_start),
+                                                      N.ptr(word), N.ptr(sent), B, L, D, 1 if mean_layers else 0, N.stream()),
+                "glr_wordpiece_segsum_rows_fwd")
+        ctx.save_for_backward(dst)
+        ctx.rows = rows
+        ctx.meta = (D, len(hs), mean_layers, [h.dtype for h in layers])
+        return word, sent
+
+    @staticmethod
+    def backward(ctx, d_word, d_sent):
+        (dst,) = ctx.saved_tensors
+        rows = ctx.rows
+        D, nl, mean_layers, dts = ctx.meta
+        dw = None if d_word is None else d_word.float().contiguous()
+        ds = None if d_sent is None else d_sent.float().contiguous()
+        out_dt = torch.bfloat16 if dts[0] == torch.bfloat16 else torch.float32
+        dh = torch.empty(rows.T, D, dtype=out_dt, device=dst.device)
+        N.check(N.lib().glr_wordpiece_segsum_rows_bwd(N.ptr(dw), N.ptr(ds), N.ptr(dst), N.ptr(rows.row_start), N.ptr(dh),
+                                                      N.dtype_code(out_dt), rows.B, rows.L, D, nl, 1 if mean_layers else 0,
+                                                      N.stream()),
+                "glr_wordpiece_segsum_rows_bwd")
+        return (None, None, None) + tuple(dh.to(dt) for dt in dts)
+
+
 def host_ids(ids):
     """caption ids as a host array WITHOUT a device sync when the trainer kept the host copy (Trainer.to_device
     attaches it as `_glr_host`); a plain `.cpu()` here would drain the stream every step (the image encoder is
@@ -241,14 +284,45 @@ class BertEncoder(nn.Module):
         self._graph_rng = rng
         return True
 
+    def _graph_fits(self, ids, attn_mask):
+        """whether this call goes through the captured graphs"""
+        return (getattr(self, "_graph", None) is not None and self.training and torch.is_grad_enabled() and attn_mask is not None
+                and self._graph_key == (tuple(ids.shape), torch.get_autocast_dtype("cuda") if torch.is_autocast_enabled("cuda") else None))
+
     def _encode(self, ids, attn_mask, token_type):
         """hidden states of the last `last_n_layers` layers, through the captured graphs when they fit this call"""
-        if (getattr(self, "_graph", None) is not None and self.training and torch.is_grad_enabled() and attn_mask is not None
-                and self._graph_key == (tuple(ids.shape), torch.get_autocast_dtype("cuda") if torch.is_autocast_enabled("cuda") else None)):
+        if self._graph_fits(ids, attn_mask):
             x = self.model.embeddings(ids, token_type)
             self._graph_rng.refresh()
             return self._graph(x, (attn_mask != 0)[:, None, None, :])
         return None
+
+    def _packed_rows(self, ids, attn_mask):
+        """(PackedRows, word-piece slots) when this call may run the layers on its real token rows only, else (None, None):
+        the K5 configuration on the GPU under bf16 autocast with every fused kernel on, host copies of ids and mask (no
+        device sync), no captured graph for this call, and a mask plan_rows accepts (models/text_rows.py)."""
+        from . import fused_attn, fused_linear, fused_ln
+        none = (None, None)
+        if not (text_rows.ENABLED and self.agg_tokens and self.last_n_layers > 1 and self.aggregate_method in ("sum", "mean")
+                and torch.is_tensor(ids) and ids.is_cuda and torch.is_tensor(attn_mask)
+                and fused_attn.ENABLED and fused_ln.ENABLED and fused_linear.ENABLED
+                and torch.is_autocast_enabled("cuda") and torch.get_autocast_dtype("cuda") == torch.bfloat16
+                and not self._graph_fits(ids, attn_mask)):
+            return none
+        ids_h, mask_h = getattr(ids, "_glr_host", None), getattr(attn_mask, "_glr_host", None)
+        if ids_h is None or mask_h is None or ids.dim() != 2 or tuple(np.shape(ids_h)) != tuple(ids.shape) \
+                or tuple(np.shape(mask_h)) != tuple(ids.shape):
+            return none
+        c = self.model.config
+        ln = self.model.encoder.layer[0].output.LayerNorm
+        if (c.hidden_size != c.num_attention_heads * 64 or c.hidden_size % 256 != 0 or not 256 <= c.hidden_size <= 1024
+                or ln.weight.dtype != torch.float32):
+            return none
+        slots = wordpiece_slots(np.asarray(ids_h), self.vocab)
+        plan = text_rows.plan_rows(mask_h, slots[0], fused_attn._max_tokens())
+        if plan is None:
+            return none
+        return text_rows.PackedRows(plan[0], plan[1], ids.shape[0], ids.shape[1], ids.device), slots
 
     def aggregate_tokens(self, embeddings, caption_ids):
         """embeddings [B, L, D] (already reduced over layers) -> word slots [B, L, D], sents."""
@@ -264,7 +338,11 @@ class BertEncoder(nn.Module):
         return out.view(B, L, -1), sents
 
     def forward(self, ids, attn_mask, token_type):
-        layers = self._encode(ids, attn_mask, token_type) if self.last_n_layers > 1 else None
+        rows, slots = self._packed_rows(ids, attn_mask)
+        if rows is not None:                    # the layers on the real token rows only; K5 below reads the packed rows
+            layers = encode_rows(self.model.encoder, self.model.embeddings(ids, token_type), rows, self.last_n_layers)
+        else:
+            layers = self._encode(ids, attn_mask, token_type) if self.last_n_layers > 1 else None
         outputs = self.model(ids, attn_mask, token_type) if layers is None else None
         fused = None
         if self.last_n_layers > 1:
@@ -279,10 +357,13 @@ class BertEncoder(nn.Module):
                 # tests and the CPU baseline of bench.py).
                 host = host_ids(ids)
                 B, L = host.shape
-                dst, starts, n_words = wordpiece_slots(host, self.vocab)
+                dst, starts, n_words = wordpiece_slots(host, self.vocab) if slots is None else slots
                 sents = SentenceBatch(host, dst, starts, n_words, self.vocab, L)
                 dst_d = N.upload(dst.astype(np.int32), layers[0].device)
-                fused = WordpieceSegSumFn.apply(dst_d, self.aggregate_method == "mean", *layers)
+                if rows is not None:
+                    fused = WordpieceSegSumRowsFn.apply(dst_d, rows, self.aggregate_method == "mean", *layers)
+                else:
+                    fused = WordpieceSegSumFn.apply(dst_d, self.aggregate_method == "mean", *layers)
                 word_embeddings = fused[0].permute(0, 2, 1)        # [B, L, D] view; permuted back below
                 sent_embeddings = fused[1]
             else:

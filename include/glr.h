@@ -287,6 +287,16 @@ int glr_wordpiece_segsum_fwd(const void* const* hidden, int n_layers, int in_dty
                              float* word_emb, float* sent_emb, int B, int L, int D, int mean_layers, void* stream);
 int glr_wordpiece_segsum_bwd(const float* d_word, const float* d_sent, const int32_t* dst, void* d_hidden,
                              int out_dtype, int B, int L, int D, int n_layers, int mean_layers, void* stream);
+/* K5 on packed hidden states [T, D] (the text encoder's real-token route): row_start int32 [B + 1] on the device, token t
+ * of sentence b is row row_start[b] + t for t < row_start[b + 1] - row_start[b]; tokens behind it are not read (their dst
+ * must be -1).  dst stays [B, L]: word_emb / sent_emb are bitwise what the padded call gives on the scattered tensor.
+ * bwd: d_hidden [T, D], every packed row is written. */
+int glr_wordpiece_segsum_rows_fwd(const void* const* hidden, int n_layers, int in_dtype, const int32_t* dst,
+                                  const int32_t* row_start, float* word_emb, float* sent_emb, int B, int L, int D,
+                                  int mean_layers, void* stream);
+int glr_wordpiece_segsum_rows_bwd(const float* d_word, const float* d_sent, const int32_t* dst, const int32_t* row_start,
+                                  void* d_hidden, int out_dtype, int B, int L, int D, int n_layers, int mean_layers,
+                                  void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * K4  attention-supervision loss on the diagonal attention maps (gloria/models/gloria_model.py:143-147):
@@ -427,6 +437,14 @@ int glr_drop_add_ln_bwd(const float* dy32, const void* dy16, const void* h16, co
                         const float* stats, const unsigned long long* mask, long long R, int H, float p_drop,
                         float* d_inp32, void* d_h16, float* workspace, float* dgamma, float* dbeta, void* dhsum, int dhsum_bf16,
                         void* stream);
+/* The forward on R rows gathered from a larger tensor: row_ids int32 [R] (device) = the row each one came from, and the
+ * Philox counter of row r is row_ids[r] * (H / 4) + quad instead of r * (H / 4) + quad - a gathered row draws the dropout
+ * bits of its original row, so y, stats and mask words equal the ungathered call's rows bit for bit.  The backward reads
+ * the stored bits: glr_drop_add_ln_bwd as it is. */
+int glr_drop_add_ln_rows_fwd(const void* h16, const float* inp32, const float* gamma, const float* beta, const int32_t* row_ids,
+                             long long R, int H, float eps, float p_drop, unsigned long long seed, unsigned long long offset,
+                             const unsigned long long* rng_cell, float* out32, void* out16, float* stats,
+                             unsigned long long* mask, void* stream);
 /* Gradients of BertEmbeddings' lookup tables (torch: embedding_dense_backward, a device sort + ~17 launches per table).
  *   glr_embedding_bwd       dW[seg_tok[u], :] = sum over k in [seg_lo[u], seg_hi[u]) of dy[order[k], :], rows added in that
  *                           order (fp32 [tokens, D] in, fp32 table out; rows of no segment keep what dW holds: pass zeros).
@@ -463,6 +481,20 @@ int glr_attn_fwd(const void* q, const void* k, const void* v, const uint8_t* key
 int glr_attn_bwd(const void* q, const void* k, const void* v, const void* o, const void* d_o, const uint8_t* key_mask,
                  const float* lse, const uint32_t* keep, int B, int n_heads, int L, int ld, int ld_o, float scale, float p_drop,
                  void* dq, void* dk, void* dv, void* stream);
+/* The same kernels on packed rows: q, k, v, o, d_o, dq, dk, dv are [T, ld] / [T, ld_o] with no pad rows, sentence b owns rows
+ * [row_start[b], row_start[b + 1]) (int32 [B + 1] on the device; row_start_host is the same array in host memory, used to
+ * check 1 <= n_b <= glr_attn_max_tokens and to size the LDS by the longest sentence - else GLR_EINVAL, nothing launched).
+ * Every key of a sentence is live (no key mask).  lse / keep keep their padded shapes and the dropout counter its padded
+ * form, ((g * 128 + r) * 32 + (c & 31)) * 2 + (c >> 6): with the same key, and zero d_o at pad rows, glr_attn_fwd / _bwd on
+ * the padded tensor with a prefix key mask give the same o, lse, keep words, dq, dk, dv at the real rows bit for bit (a
+ * masked key adds exact zeros).  Rows >= n_b of a sentence's lse / keep block carry no information. */
+int glr_attn_rows_fwd(const void* q, const void* k, const void* v, const int32_t* row_start, const int32_t* row_start_host, int B,
+                      int n_heads, int ld, int ld_o, float scale, float p_drop, unsigned long long seed,
+                      unsigned long long offset, const unsigned long long* rng_cell, void* o, float* lse, uint32_t* keep,
+                      void* stream);
+int glr_attn_rows_bwd(const void* q, const void* k, const void* v, const void* o, const void* d_o, const int32_t* row_start,
+                      const int32_t* row_start_host, const float* lse, const uint32_t* keep, int B, int n_heads, int ld, int ld_o,
+                      float scale, float p_drop, void* dq, void* dk, void* dv, void* stream);
 
 /* The same operation for captions of up to glr_attn_long_max_tokens() = 512 tokens (1 <= L <= 512; csrc/glr_attn_long.hip):
  * one workgroup per (sentence, head, 128-row block) and pass, the other side streamed through LDS in 128-token blocks

@@ -1,7 +1,9 @@
 """Micro-benchmark: the attention kernels (glr_attn_fwd / _bwd up to 128 tokens, glr_attn_long_fwd / _bwd up to 512)
 against torch's scaled_dot_product_attention on the BERT shape of the training step (B=256, 12 heads, 97 tokens, dropout
 0.1).  B and L come from the environment: `L=258 B=32 python tools/bench_attn.py` is the text leg of scope config 5;
-FULL=1 makes every key live instead of the ragged prefixes of 6..41 tokens (the long kernels skip masked key blocks)."""
+FULL=1 makes every key live instead of the ragged prefixes of 6..41 tokens (the long kernels skip masked key blocks).
+ROWS=1: the packed-rows kernels (glr_attn_rows_fwd / _bwd) at the caption lengths of bench.py's batch against the padded
+short kernels on the same captions, both on one query|key|value tensor."""
 import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "gloria-nlp-project_amd"))
@@ -10,6 +12,42 @@ from gloria.models import fused_attn as FA
 B, nh, L = int(os.environ.get("B", 256)), 12, int(os.environ.get("L", 97))
 H = nh * 64
 dev = "cuda:0"
+
+
+def rows_mode():
+    import numpy as np
+    from gloria.datasets.synthetic import make_batch
+    from gloria.models.text_rows import PackedRows, plan_rows
+    mask = make_batch(B, seed=1234, lengths="words")["attention_mask"].numpy()
+    Lb = mask.shape[1]
+    plan = plan_rows(mask, np.where(mask != 0, 0, -1), 128)
+    rows = PackedRows(plan[0], plan[1], B, Lb, dev)
+    pad = torch.randn(B, Lb, 3 * H, device=dev).bfloat16().requires_grad_(True)
+    packed = pad.detach().view(B * Lb, 3 * H)[rows.row_ids64].contiguous().requires_grad_(True)
+    km = torch.from_numpy(mask != 0).to(dev)
+    d_pad, d_rows = torch.randn(B, Lb, H, device=dev).bfloat16(), torch.randn(rows.T, H, device=dev).bfloat16()
+    runs = (("padded", pad, d_pad, lambda: FA.self_attention_packed(pad, km, nh, 0.1, True)),
+            ("rows  ", packed, d_rows, lambda: FA.self_attention_rows(packed, rows, nh, 0.1, True)))
+    print(f"B {B} L {Lb} real rows {rows.T} of {B * Lb}, longest {rows.longest}")
+    for name, x, d, fn in runs:
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
+        tf = tb = 0.0
+        for it in range(13):
+            x.grad = None
+            ev[0].record()
+            o = fn()
+            ev[1].record()
+            o.backward(d)
+            ev[2].record()
+            torch.cuda.synchronize()
+            if it >= 3:
+                tf += ev[0].elapsed_time(ev[1]); tb += ev[1].elapsed_time(ev[2])
+        print(f"{name} fwd {tf / 10 * 1e3:.1f} us  bwd {tb / 10 * 1e3:.1f} us", flush=True)
+
+
+if os.environ.get("ROWS", "0") == "1":
+    rows_mode()
+    sys.exit(0)
 q, k, v = (torch.randn(B, L, H, device=dev).bfloat16().requires_grad_(True) for _ in range(3))
 d_o = torch.randn(B, L, H, device=dev).bfloat16()
 lens = torch.randint(6, 42, (B,), device=dev)

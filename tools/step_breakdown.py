@@ -41,6 +41,8 @@ def main():
     ap.add_argument("trace")
     ap.add_argument("--steps", type=int, default=4)
     ap.add_argument("--top", type=int, default=25)
+    ap.add_argument("--sum", action="append", default=[], metavar="REGEX",
+                    help="also print the per-step time and launches of the kernels whose name matches (repeatable)")
     a = ap.parse_args()
     rows = []
     if a.trace.endswith(".db"):                      # rocprofv3's default rocpd (sqlite) output
@@ -77,6 +79,9 @@ def main():
           f"({len(sel) // a.steps} launches per step)")
     for fam, t in sorted(fam_t.items(), key=lambda kv: -kv[1]):
         print(f"  {t / a.steps:8.2f} ms  {100 * t / busy:5.1f}%  {fam}")
+    for pat in a.sum:
+        hit = [n for n in ker_t if re.search(pat, n)]
+        print(f"  {sum(ker_t[n] for n in hit) / a.steps:8.2f} ms  {sum(ker_n[n] for n in hit) / a.steps:7.1f} launches  kernels matching /{pat}/")
     print("top kernels (ms per step, launches per step):")
     for n, t in sorted(ker_t.items(), key=lambda kv: -kv[1])[:a.top]:
         print(f"  {t / a.steps:8.3f}  {ker_n[n] / a.steps:7.1f}  {n[:130]}")
