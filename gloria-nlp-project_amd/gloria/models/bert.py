@@ -49,11 +49,6 @@ class BertEmbeddings(nn.Module):
         return self.dropout(self.LayerNorm(x))
 
 
-def _row_ids(bias):
-    """the layers take a PackedRows in place of the key mask when they run on real token rows only"""
-    return bias.row_ids if isinstance(bias, PackedRows) else None
-
-
 class BertSelfAttention(nn.Module):
     def __init__(self, c):
         super().__init__()
@@ -63,22 +58,23 @@ class BertSelfAttention(nn.Module):
         self.value = nn.Linear(c.hidden_size, c.hidden_size)
         self.p = c.attention_probs_dropout_prob
 
-    def forward(self, x, bias):
-        # bias: bool key mask [B, 1, 1, L] (True = attend) or None.  softmax(QK^T) -> dropout -> .V on the Linear outputs
+    def _qkv_weights(self):
+        """weight [3H, H] and bias [3H] of the three Linears as ONE query|key|value Linear"""
+        return (torch.cat([self.query.weight, self.key.weight, self.value.weight], 0),
+                torch.cat([self.query.bias, self.key.bias, self.value.bias], 0))
+
+    def forward(self, x, keys, on_rows=False):
+        # keys: bool key mask [B, 1, 1, L] (True = attend) or None.  softmax(QK^T) -> dropout -> .V on the Linear outputs
         # as they are: one HIP kernel per direction for short captions under bf16 autocast (models/fused_attn.py)
-        if isinstance(bias, PackedRows):
-            # x: [T, H], the real token rows only (models/text_rows.py); every key of a sentence is live
-            w = torch.cat([self.query.weight, self.key.weight, self.value.weight], 0)
-            b_ = torch.cat([self.query.bias, self.key.bias, self.value.bias], 0)
-            return self_attention_rows(linear(x, w, b_), bias, self.nh, self.p, self.training)
+        if on_rows:
+            # keys: a PackedRows; x: [T, H], the real token rows only (models/text_rows.py); every key of a sentence is live
+            return self_attention_rows(linear(x, *self._qkv_weights()), keys, self.nh, self.p, self.training)
         B, L, H = x.shape
-        key_mask = None if bias is None else bias.reshape(B, L)
+        key_mask = None if keys is None else keys.reshape(B, L)
         if packed_fusable(x, self.nh, H, L, key_mask):
             # one [H -> 3H] GEMM instead of three [H -> H] ones (at 25k tokens x 768 the library runs the small ones at
             # under 200 TFLOP/s), and the kernels read / write the packed tensor in place: no split, no gradient adds
-            w = torch.cat([self.query.weight, self.key.weight, self.value.weight], 0)
-            b_ = torch.cat([self.query.bias, self.key.bias, self.value.bias], 0)
-            return self_attention_packed(linear(x, w, b_), key_mask, self.nh, self.p, self.training)
+            return self_attention_packed(linear(x, *self._qkv_weights()), key_mask, self.nh, self.p, self.training)
         return self_attention(self.query(x), self.key(x), self.value(x), key_mask, self.nh, self.p, self.training)
 
 
@@ -101,9 +97,10 @@ class BertAttention(nn.Module):
         self.self = BertSelfAttention(c)
         self.output = BertSelfOutput(c)
 
-    def forward(self, x, bias, x16=None):
+    def forward(self, x, keys, x16=None, row_ids=None):
         # x16: the bf16 copy of x the fused sub-layer epilogue already wrote (the operand autocast would cast x to)
-        return self.output(self.self(x if x16 is None else x16, bias), x, _row_ids(bias))
+        # row_ids: given by BertLayer exactly when keys is a PackedRows
+        return self.output(self.self(x if x16 is None else x16, keys, row_ids is not None), x, row_ids)
 
 
 class BertIntermediate(nn.Module):
@@ -133,16 +130,27 @@ class BertLayer(nn.Module):
         self.intermediate = BertIntermediate(c)
         self.output = BertOutput(c)
 
-    def forward(self, x, bias, x16=None):
-        """(hidden state fp32, its bf16 copy or None)"""
-        a, a16 = self.attention(x, bias, x16)
-        return self.output(self.intermediate(a if a16 is None else a16), a, _row_ids(bias))
+    def forward(self, x, keys, x16=None):
+        """(hidden state fp32, its bf16 copy or None).  keys: the bool key mask [B, 1, 1, L], None, or - when x holds the
+        real token rows only - a PackedRows in its place; this is the one place that asks which"""
+        row_ids = keys.row_ids if isinstance(keys, PackedRows) else None
+        a, a16 = self.attention(x, keys, x16, row_ids)
+        return self.output(self.intermediate(a if a16 is None else a16), a, row_ids)
 
 
 class BertEncoderStack(nn.Module):
     def __init__(self, c):
         super().__init__()
         self.layer = nn.ModuleList([BertLayer(c) for _ in range(c.num_hidden_layers)])
+
+
+def run_layers(encoder, x, keys):
+    """every layer of the stack on x -> the list of the hidden states after each layer (keys: see BertLayer.forward)"""
+    hidden, x16 = [], None
+    for layer in encoder.layer:
+        x, x16 = layer(x, keys, x16)
+        hidden.append(x)
+    return hidden
 
 
 class BertStackPath(nn.Module):
@@ -156,11 +164,7 @@ class BertStackPath(nn.Module):
         self.n_out = int(n_out)
 
     def forward(self, x, key_mask4):
-        hidden, x16 = [], None
-        for layer in self.encoder.layer:
-            x, x16 = layer(x, key_mask4, x16)
-            hidden.append(x)
-        return tuple(hidden[-self.n_out:])
+        return tuple(run_layers(self.encoder, x, key_mask4)[-self.n_out:])
 
 
 def encode_rows(encoder, x, rows, n_out):
@@ -168,11 +172,7 @@ def encode_rows(encoder, x, rows, n_out):
     states (the gathered embedding output counts as the first, as in BertModel.forward) as [T, H].  One gather in front;
     autograd scatters the gradient back to the padded embedding output."""
     x = x.reshape(rows.B * rows.L, x.shape[-1]).index_select(0, rows.row_ids64)
-    hidden, x16 = [x], None
-    for layer in encoder.layer:
-        x, x16 = layer(x, rows, x16)
-        hidden.append(x)
-    return tuple(hidden[-int(n_out):])
+    return tuple(([x] + run_layers(encoder, x, rows))[-int(n_out):])
 
 
 class BertPooler(nn.Module):
@@ -212,12 +212,8 @@ class BertModel(nn.Module):
 
     def forward(self, ids, attention_mask=None, token_type_ids=None):
         x = self.embeddings(ids, token_type_ids)
-        bias = None
+        keys = None
         if attention_mask is not None:          # boolean key mask (True = attend), broadcast over heads/queries
-            bias = (attention_mask != 0)[:, None, None, :]
-        hidden = [x]
-        x16 = None
-        for layer in self.encoder.layer:
-            x, x16 = layer(x, bias, x16)
-            hidden.append(x)
-        return x, self.pooler(x), tuple(hidden)
+            keys = (attention_mask != 0)[:, None, None, :]
+        hidden = [x] + run_layers(self.encoder, x, keys)
+        return hidden[-1], self.pooler(hidden[-1]), tuple(hidden)

@@ -13,9 +13,9 @@ scores in a kernel that is VALU-bound, so the per-score draw is the cheaper mixe
 counter.  `GLR_FUSED_ATTN=0` switches the kernels off.
 
 Captions of 129 to 512 tokens run the block-streaming kernels of csrc/glr_attn_long.hip (glr_attn_long_fwd / _bwd) through
-the same two autograd functions: lse and the keep bits are sized by Lp = L rounded up to 128 ([B * nh, Lp] and
-[B * nh, Lp, Lp / 32]: 32 KB of keep bits per sentence x head at 512 tokens, held until the backward), and the dropout
-counter is the one documented in include/glr.h.  `GLR_FUSED_ATTN_LONG` (0 / 1, default 1: DESIGN.md has the measurement
+the same autograd function (`_SelfAttn`, whatever the layout: `_layout` gives the pointers, `_route` the kernel pair): lse
+and the keep bits are sized by Lp = L rounded up to 128 ([B * nh, Lp] and [B * nh, Lp, Lp / 32]: 32 KB of keep bits per
+sentence x head at 512 tokens, held until the backward), and the dropout counter is the one documented in include/glr.h.  `GLR_FUSED_ATTN_LONG` (0 / 1, default 1: DESIGN.md has the measurement
 behind it - faster than torch on ragged batches, slower when every key of the padded length is live) switches only that
 range; with it off those lengths run torch's scaled_dot_product_attention as every other unsupported case does."""
 
@@ -27,6 +27,7 @@ import torch.nn.functional as F
 
 from .. import _native as N
 from .rng import philox_args
+from .text_rows import PackedRows
 
 ENABLED = os.environ.get("GLR_FUSED_ATTN", "1") != "0"
 LONG_ENABLED = os.environ.get("GLR_FUSED_ATTN_LONG", "1") != "0"
@@ -61,132 +62,90 @@ def _entry(L):
     return L_.glr_attn_long_fwd, L_.glr_attn_long_bwd, "glr_attn_long", (L + 127) // 128 * 128
 
 
+def heads_ok(hidden, nh):
+    """the head geometry the kernels take: heads of 64 features"""
+    return hidden == nh * 64
+
+
+def _layout(tensors):
+    """(query, key, value base addresses, their row stride, H, shape of o) of split q, k, v [.., H] or of ONE packed
+    [.., 3H] tensor (query | key | value columns, bf16: the blocks start 2H and 4H bytes in)"""
+    if len(tensors) == 3:
+        q, k, v = tensors
+        return q.data_ptr(), k.data_ptr(), v.data_ptr(), q.shape[-1], q.shape[-1], q.shape
+    (qkv,) = tensors
+    base, H = qkv.data_ptr(), qkv.shape[-1] // 3
+    return base, base + 2 * H, base + 4 * H, 3 * H, H, qkv.shape[:-1] + (H,)
+
+
+def _route(keys, nh, o_shape):
+    """(forward, backward, name, rows of lse / keep, arguments that locate the sentences, dimension arguments) of the
+    kernel pair for a key mask (bool [B, L] or None) over o_shape = [B, L, H], or for a PackedRows over [T, H]: the short
+    kernels with every key live, lse / keep in the shapes the padded call of the same sentences has"""
+    if isinstance(keys, PackedRows):
+        L_ = N.lib()
+        return (L_.glr_attn_rows_fwd, L_.glr_attn_rows_bwd, "glr_attn_rows", _entry(keys.longest)[3],
+                (N.ptr(keys.row_start), keys.row_start_host.ctypes.data), (keys.B, nh))
+    return _entry(o_shape[1]) + ((N.ptr(keys),), (o_shape[0], nh, o_shape[1]))
+
+
 class _SelfAttn(torch.autograd.Function):
+    """tensors: q, k, v [B, L, H], or ONE [B, L, 3H] tensor (the output of a single fused Linear; the backward writes
+    dq | dk | dv straight into its gradient, row stride 3H on both sides), or with keys a PackedRows ONE [T, 3H] tensor of
+    real token rows only (models/text_rows.py): sentence b owns rows row_start[b] .. row_start[b + 1].  The dropout counter
+    keeps its padded form there, so a sentence draws the bits the padded kernel draws for it."""
+
     @staticmethod
-    def forward(ctx, q, k, v, key_mask, nh, p, scale):
-        B, L, H = q.shape
-        fwd, _, name, Lp = _entry(L)
-        dev = q.device
-        o = torch.empty_like(q)
-        lse = torch.empty(B * nh, Lp, dtype=torch.float32, device=dev)
-        keep = torch.empty(B * nh, Lp, Lp // 32, dtype=torch.int32, device=dev) if p > 0 else None
+    def forward(ctx, keys, nh, p, scale, *tensors):
+        qp, kp, vp, ld, H, o_shape = _layout(tensors)
+        fwd, _, name, Lp, where, dims = _route(keys, nh, o_shape)
+        dev = tensors[0].device
+        o = torch.empty(o_shape, dtype=tensors[0].dtype, device=dev)
+        lse = torch.empty(dims[0] * nh, Lp, dtype=torch.float32, device=dev)
+        keep = torch.empty(dims[0] * nh, Lp, Lp // 32, dtype=torch.int32, device=dev) if p > 0 else None
         seed, off, cell = philox_args(dev) if p > 0 else (0, 0, None)
-        N.check(fwd(N.ptr(q), N.ptr(k), N.ptr(v), N.ptr(key_mask), B, nh, L, H, H, float(scale), float(p), seed, off,
-                    cell, N.ptr(o), N.ptr(lse), N.ptr(keep), N.stream()), name + "_fwd")
-        ctx.save_for_backward(q, k, v, o, lse, keep, key_mask)
-        ctx.meta = (nh, float(p), float(scale))
+        N.check(fwd(qp, kp, vp, *where, *dims, ld, H, float(scale), float(p), seed, off, cell, N.ptr(o), N.ptr(lse),
+                    N.ptr(keep), N.stream()), name + "_fwd")
+        rows = keys if isinstance(keys, PackedRows) else None
+        ctx.save_for_backward(*tensors, o, lse, keep, None if rows is not None else keys)
+        ctx.meta = (rows, nh, float(p), float(scale))
         return o
 
     @staticmethod
     def backward(ctx, d_o):
-        q, k, v, o, lse, keep, key_mask = ctx.saved_tensors
-        nh, p, scale = ctx.meta
-        B, L, H = q.shape
-        _, bwd, name, _ = _entry(L)
+        *tensors, o, lse, keep, key_mask = ctx.saved_tensors
+        rows, nh, p, scale = ctx.meta
+        qp, kp, vp, ld, H, o_shape = _layout(tensors)
+        _, bwd, name, _, where, dims = _route(key_mask if rows is None else rows, nh, o_shape)
         d_o = d_o.to(torch.bfloat16).contiguous()
-        dq, dk, dv = torch.empty_like(q), torch.empty_like(q), torch.empty_like(q)
-        N.check(bwd(N.ptr(q), N.ptr(k), N.ptr(v), N.ptr(o), N.ptr(d_o), N.ptr(key_mask), N.ptr(lse), N.ptr(keep),
-                    B, nh, L, H, H, scale, p, N.ptr(dq), N.ptr(dk), N.ptr(dv), N.stream()), name + "_bwd")
-        return dq, dk, dv, None, None, None, None
-
-
-class _SelfAttnPacked(torch.autograd.Function):
-    """the same kernels on ONE [B, L, 3H] tensor (query | key | value columns): the output of a single fused Linear.
-    The backward writes dq | dk | dv straight into the gradient of that tensor (row stride 3H on both sides)."""
-
-    @staticmethod
-    def forward(ctx, qkv, key_mask, nh, p, scale):
-        B, L, H3 = qkv.shape
-        H = H3 // 3
-        fwd, _, name, Lp = _entry(L)
-        dev = qkv.device
-        o = torch.empty(B, L, H, dtype=qkv.dtype, device=dev)
-        lse = torch.empty(B * nh, Lp, dtype=torch.float32, device=dev)
-        keep = torch.empty(B * nh, Lp, Lp // 32, dtype=torch.int32, device=dev) if p > 0 else None
-        seed, off, cell = philox_args(dev) if p > 0 else (0, 0, None)
-        base = qkv.data_ptr()
-        N.check(fwd(N.c_void_p(base), N.c_void_p(base + 2 * H), N.c_void_p(base + 4 * H), N.ptr(key_mask), B, nh, L, H3, H,
-                    float(scale), float(p), seed, off, cell, N.ptr(o), N.ptr(lse), N.ptr(keep), N.stream()), name + "_fwd")
-        ctx.save_for_backward(qkv, o, lse, keep, key_mask)
-        ctx.meta = (nh, float(p), float(scale))
-        return o
-
-    @staticmethod
-    def backward(ctx, d_o):
-        qkv, o, lse, keep, key_mask = ctx.saved_tensors
-        nh, p, scale = ctx.meta
-        B, L, H3 = qkv.shape
-        H = H3 // 3
-        _, bwd, name, _ = _entry(L)
-        d_o = d_o.to(torch.bfloat16).contiguous()
-        dqkv = torch.empty_like(qkv)
-        base, dbase = qkv.data_ptr(), dqkv.data_ptr()
-        N.check(bwd(N.c_void_p(base), N.c_void_p(base + 2 * H), N.c_void_p(base + 4 * H), N.ptr(o), N.ptr(d_o),
-                    N.ptr(key_mask), N.ptr(lse), N.ptr(keep), B, nh, L, H3, H, scale, p, N.c_void_p(dbase),
-                    N.c_void_p(dbase + 2 * H), N.c_void_p(dbase + 4 * H), N.stream()), name + "_bwd")
-        return dqkv, None, None, None, None
-
-
-class _SelfAttnRows(torch.autograd.Function):
-    """the short kernels on a packed [T, 3H] query|key|value tensor of real token rows only (models/text_rows.py):
-    sentence b owns rows row_start[b] .. row_start[b + 1], every key is live.  lse / keep keep the padded shapes and the
-    dropout counter its padded form, so a sentence draws the bits the padded kernel draws for it."""
-
-    @staticmethod
-    def forward(ctx, qkv, rows, nh, p, scale):
-        T, H3 = qkv.shape
-        H = H3 // 3
-        dev = qkv.device
-        o = torch.empty(T, H, dtype=qkv.dtype, device=dev)
-        lse = torch.empty(rows.B * nh, 128, dtype=torch.float32, device=dev)
-        keep = torch.empty(rows.B * nh, 128, 4, dtype=torch.int32, device=dev) if p > 0 else None
-        seed, off, cell = philox_args(dev) if p > 0 else (0, 0, None)
-        base = qkv.data_ptr()
-        N.check(N.lib().glr_attn_rows_fwd(N.c_void_p(base), N.c_void_p(base + 2 * H), N.c_void_p(base + 4 * H),
-                                          N.ptr(rows.row_start), rows.row_start_host.ctypes.data, rows.B, nh, H3, H,
-                                          float(scale), float(p), seed, off, cell, N.ptr(o), N.ptr(lse), N.ptr(keep),
-                                          N.stream()), "glr_attn_rows_fwd")
-        ctx.save_for_backward(qkv, o, lse, keep)
-        ctx.rows = rows
-        ctx.meta = (nh, float(p), float(scale))
-        return o
-
-    @staticmethod
-    def backward(ctx, d_o):
-        qkv, o, lse, keep = ctx.saved_tensors
-        rows = ctx.rows
-        nh, p, scale = ctx.meta
-        H = qkv.shape[1] // 3
-        d_o = d_o.to(torch.bfloat16).contiguous()
-        dqkv = torch.empty_like(qkv)
-        base, dbase = qkv.data_ptr(), dqkv.data_ptr()
-        N.check(N.lib().glr_attn_rows_bwd(N.c_void_p(base), N.c_void_p(base + 2 * H), N.c_void_p(base + 4 * H), N.ptr(o),
-                                          N.ptr(d_o), N.ptr(rows.row_start), rows.row_start_host.ctypes.data, N.ptr(lse),
-                                          N.ptr(keep), rows.B, nh, 3 * H, H, scale, p, N.c_void_p(dbase),
-                                          N.c_void_p(dbase + 2 * H), N.c_void_p(dbase + 4 * H), N.stream()),
-                "glr_attn_rows_bwd")
-        return dqkv, None, None, None, None
+        grads = tuple(torch.empty_like(t) for t in tensors)
+        N.check(bwd(qp, kp, vp, N.ptr(o), N.ptr(d_o), *where, N.ptr(lse), N.ptr(keep), *dims, ld, H, scale, p,
+                    *_layout(grads)[:3], N.stream()), name + "_bwd")
+        return (None, None, None, None) + grads
 
 
 def self_attention_rows(qkv, rows, nh, p, training):
     """qkv: bf16 [T, 3H] (query | key | value columns) of the packed rows of `rows` -> context [T, H]"""
-    if qkv.dtype != torch.bfloat16 or qkv.shape[0] != rows.T or qkv.shape[1] != 3 * nh * 64:
+    if qkv.dtype != torch.bfloat16 or qkv.shape[0] != rows.T or qkv.shape[1] % 3 or not heads_ok(qkv.shape[1] // 3, nh):
         raise RuntimeError("self_attention_rows: a bf16 [T, 3 * n_heads * 64] tensor of the plan's rows is required")
-    return _SelfAttnRows.apply(qkv.contiguous(), rows, nh, p if training else 0.0, 1.0 / 8.0)
+    return _SelfAttn.apply(rows, nh, p if training else 0.0, 1.0 / 8.0, qkv.contiguous())
+
+
+def _mask_ok(key_mask):
+    return key_mask is None or (key_mask.dtype == torch.bool and key_mask.is_contiguous())
 
 
 def _fusable(q, k, v, key_mask, nh):
     B, L, H = q.shape
-    return (ENABLED and q.is_cuda and q.dtype == k.dtype == v.dtype == torch.bfloat16 and H == nh * 64 and _length_ok(L)
+    return (ENABLED and q.is_cuda and q.dtype == k.dtype == v.dtype == torch.bfloat16 and heads_ok(H, nh) and _length_ok(L)
             and q.is_contiguous() and k.is_contiguous() and v.is_contiguous()
-            and (key_mask is None or (key_mask.dtype == torch.bool and tuple(key_mask.shape) == (B, L) and key_mask.is_contiguous())))
+            and _mask_ok(key_mask) and (key_mask is None or tuple(key_mask.shape) == (B, L)))
 
 
 def packed_fusable(x, nh, hidden, L, key_mask):
     """whether BertSelfAttention may run ONE query|key|value Linear and the packed kernels on input x"""
     return (ENABLED and x.is_cuda and torch.is_autocast_enabled("cuda") and torch.get_autocast_dtype("cuda") == torch.bfloat16
-            and hidden == nh * 64 and _length_ok(L)
-            and (key_mask is None or (key_mask.dtype == torch.bool and key_mask.is_contiguous())))
+            and heads_ok(hidden, nh) and _length_ok(L) and _mask_ok(key_mask))
 
 
 def self_attention_packed(qkv, key_mask, nh, p, training):
@@ -194,7 +153,7 @@ def self_attention_packed(qkv, key_mask, nh, p, training):
     if not _length_ok(qkv.shape[1]):                        # a length no enabled kernel takes: the three column blocks
         q, k, v = (t.contiguous() for t in qkv.split(qkv.shape[2] // 3, dim=-1))
         return self_attention(q, k, v, key_mask, nh, p, training)
-    return _SelfAttnPacked.apply(qkv.contiguous(), key_mask, nh, p if training else 0.0, 1.0 / 8.0)
+    return _SelfAttn.apply(key_mask, nh, p if training else 0.0, 1.0 / 8.0, qkv.contiguous())
 
 
 def self_attention(q, k, v, key_mask, nh, p, training):
@@ -202,7 +161,7 @@ def self_attention(q, k, v, key_mask, nh, p, training):
     B, L, H = q.shape
     hd = H // nh
     if _fusable(q, k, v, key_mask, nh):
-        return _SelfAttn.apply(q, k, v, key_mask, nh, p if training else 0.0, 1.0 / math.sqrt(hd))
+        return _SelfAttn.apply(key_mask, nh, p if training else 0.0, 1.0 / math.sqrt(hd), q, k, v)
     bias = None if key_mask is None else key_mask[:, None, None, :]
     qh, kh, vh = (t.view(B, L, nh, hd).transpose(1, 2) for t in (q, k, v))
     o = F.scaled_dot_product_attention(qh, kh, vh, attn_mask=bias, dropout_p=p if training else 0.0)

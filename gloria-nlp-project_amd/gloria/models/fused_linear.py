@@ -18,28 +18,10 @@ import torch
 import torch.nn.functional as F
 
 from .. import _native as N
+from .workspace import make_workspace
 
 ENABLED = os.environ.get("GLR_FUSED_LINEAR", "1") != "0"
-_WS = {}            # (device index, stream) -> fp32 workspace: launches of one stream only (see fused_bn)
-_WS_FLOATS = {}
-
-
-def _workspace(dev, R, C):
-    n = _WS_FLOATS.get((R, C))
-    if n is None:
-        if len(_WS_FLOATS) >= 64:        # the packed text route changes R every step: the cache stays small
-            _WS_FLOATS.clear()
-        n = _WS_FLOATS[(R, C)] = int(N.lib().glr_colsum_workspace_floats(R, C))
-    if n == 0:
-        return None
-    if torch.cuda.is_current_stream_capturing():        # a graph keeps its own: the shared one may be replaced later
-        return torch.empty(n, dtype=torch.float32, device=dev)
-    key = (dev.index, N.stream())
-    ws = _WS.get(key)
-    if ws is None or ws.numel() < n:
-        ws = torch.empty(max(n, 1 << 20), dtype=torch.float32, device=dev)
-        _WS[key] = ws
-    return ws
+_workspace = make_workspace("glr_colsum_workspace_floats", 1 << 20)      # (dev, R, C) -> colsum's partial sums, None: no kernel
 
 
 def colsum(dy2):

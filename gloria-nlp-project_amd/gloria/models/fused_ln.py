@@ -18,28 +18,10 @@ import torch.nn.functional as F
 
 from .. import _native as N
 from .rng import philox_args
+from .workspace import make_workspace
 
 ENABLED = os.environ.get("GLR_FUSED_LN", "1") != "0"
-_WS = {}            # (device index, stream) -> fp32 workspace: launches of one stream only (see fused_bn)
-
-
-_WS_FLOATS = {}
-
-
-def _workspace(dev, R, H):
-    n = _WS_FLOATS.get((R, H))
-    if n is None:
-        if len(_WS_FLOATS) >= 64:        # the packed text route changes R every step: the cache stays small
-            _WS_FLOATS.clear()
-        n = _WS_FLOATS[(R, H)] = int(N.lib().glr_ln_workspace_floats(R, H))
-    if torch.cuda.is_current_stream_capturing():        # a graph keeps its own: the shared one may be replaced later
-        return torch.empty(n, dtype=torch.float32, device=dev)
-    key = (dev.index, N.stream())
-    ws = _WS.get(key)
-    if ws is None or ws.numel() < n:
-        ws = torch.empty(max(n, 1 << 21), dtype=torch.float32, device=dev)
-        _WS[key] = ws
-    return ws
+_workspace = make_workspace("glr_ln_workspace_floats", 1 << 21)          # (dev, R, H) -> the backward's partial sums
 
 
 class _DropAddLN(torch.autograd.Function):
@@ -107,21 +89,25 @@ def c_off(t, n_elems):
     return N.c_void_p(t.data_ptr() + 4 * n_elems)
 
 
+def ln_ok(H, ln):
+    """a hidden size and LayerNorm the kernels take: 256 / 512 / 768 / 1024 features, fp32 weight and bias"""
+    return (H % 256 == 0 and 256 <= H <= 1024 and ln.elementwise_affine and ln.weight.dtype == torch.float32
+            and ln.bias is not None and ln.bias.dtype == torch.float32 and tuple(ln.normalized_shape) == (H,))
+
+
 def _fusable(h, inp, ln):
-    H = h.shape[-1]
     return (ENABLED and h.is_cuda and h.dtype == torch.bfloat16 and inp.dtype == torch.float32 and h.shape == inp.shape
-            and H % 256 == 0 and 256 <= H <= 1024 and ln.elementwise_affine and ln.weight.dtype == torch.float32
-            and ln.bias is not None and ln.bias.dtype == torch.float32 and tuple(ln.normalized_shape) == (H,)
-            and h.is_contiguous() and inp.is_contiguous())
+            and ln_ok(h.shape[-1], ln) and h.is_contiguous() and inp.is_contiguous())
 
 
 def drop_add_ln(h, inp, ln, p, training, h_bias=None, row_ids=None):
-    """(LayerNorm(dropout(h) + inp) in fp32, the same rounded to bf16 or None).  h_bias: see _DropAddLN.forward - only
-    pass it when `fusable(h, inp, ln)` (the unfused path has no gradient to give it)."""
+    """(LayerNorm(dropout(h) + inp) in fp32, the same rounded to bf16 or None).  h_bias, row_ids: see _DropAddLN.forward -
+    only pass them when `_fusable(h, inp, ln)` (the unfused path has no gradient to give the one and draws torch's
+    dropout stream, not the masks of the rows the other names)."""
     if _fusable(h, inp, ln):
         return _DropAddLN.apply(h, inp, ln.weight, ln.bias, ln.eps, p if training else 0.0, h_bias, row_ids)
-    if h_bias is not None:
-        raise RuntimeError("drop_add_ln: h_bias given on the unfused path")
+    if h_bias is not None or row_ids is not None:
+        raise RuntimeError("drop_add_ln: %s given on the unfused path" % ("h_bias" if h_bias is not None else "row_ids"))
     return ln(F.dropout(h, p, training) + inp), None
 
 
@@ -130,9 +116,7 @@ def dense_drop_add_ln(dense, x, inp, ln, p, training, row_ids=None):
     Linear's backward skips its bias gradient and the LayerNorm backward kernel supplies it (one pass over d_h less)."""
     from .fused_linear import linear, linear_fusable
     H = dense.out_features
-    if (ENABLED and x.is_cuda and linear_fusable(x, dense.weight, dense.bias) and inp.dtype == torch.float32
-            and H % 256 == 0 and 256 <= H <= 1024 and ln.elementwise_affine and ln.weight.dtype == torch.float32
-            and ln.bias is not None and ln.bias.dtype == torch.float32 and tuple(ln.normalized_shape) == (H,)
+    if (ENABLED and x.is_cuda and linear_fusable(x, dense.weight, dense.bias) and inp.dtype == torch.float32 and ln_ok(H, ln)
             and inp.is_contiguous() and inp.shape[:-1] == x.shape[:-1] and inp.shape[-1] == H):
         h = linear(x, dense.weight, dense.bias, bias_grad_from_epilogue=True)
         return _DropAddLN.apply(h, inp, ln.weight, ln.bias, ln.eps, p if training else 0.0, dense.bias, row_ids)

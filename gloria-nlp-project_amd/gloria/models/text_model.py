@@ -13,6 +13,7 @@ What changes underneath:
     path never touches Python strings.
 """
 
+import ctypes
 import os
 
 import numpy as np
@@ -124,83 +125,62 @@ def wordpiece_slots(ids: np.ndarray, vocab: Vocab):
     return dst, starts, n_words
 
 
+def _segsum(rows, direction):
+    """(entry point, its name, the row-plan argument it takes after dst) of K5 on padded (rows=None) or packed hidden states"""
+    name = "glr_wordpiece_segsum_%s%s" % ("" if rows is None else "rows_", direction)
+    return getattr(N.lib(), name), name, () if rows is None else (N.ptr(rows.row_start),)
+
+
 class WordpieceSegSumFn(torch.autograd.Function):
-    """K5: (hidden states of the last layers, token -> word-slot index) -> word_emb [B, D, L], sent_emb [B, D]."""
-
-    @staticmethod
-    def forward(ctx, dst, mean_layers, *layers):
-        from .. import _native as N
-        import ctypes
-        hs = [h.detach().contiguous() for h in layers]
-        if hs[0].dtype not in (torch.float32, torch.bfloat16):
-            hs = [h.float() for h in hs]
-        B, L, D = hs[0].shape
-        dev = hs[0].device
-        word = torch.empty(B, D, L, dtype=torch.float32, device=dev)
-        sent = torch.empty(B, D, dtype=torch.float32, device=dev)
-        ptrs = (ctypes.c_void_p * len(hs))(*[h.data_ptr() for h in hs])
-        N.check(N.lib().glr_wordpiece_segsum_fwd(ptrs, len(hs), N.dtype_code(hs[0].dtype), N.ptr(dst), N.ptr(word),
-                                                 N.ptr(sent), B, L, D, 1 if mean_layers else 0, N.stream()),
-                "glr_wordpiece_segsum_fwd")
-        ctx.save_for_backward(dst)
-        ctx.meta = (B, L, D, len(hs), mean_layers, [h.dtype for h in layers])
-        return word, sent
-
-    @staticmethod
-    def backward(ctx, d_word, d_sent):
-        from .. import _native as N
-        (dst,) = ctx.saved_tensors
-        B, L, D, nl, mean_layers, dts = ctx.meta
-        dw = None if d_word is None else d_word.float().contiguous()
-        ds = None if d_sent is None else d_sent.float().contiguous()
-        out_dt = torch.bfloat16 if dts[0] == torch.bfloat16 else torch.float32
-        dh = torch.empty(B, L, D, dtype=out_dt, device=dst.device)
-        N.check(N.lib().glr_wordpiece_segsum_bwd(N.ptr(dw), N.ptr(ds), N.ptr(dst), N.ptr(dh), N.dtype_code(out_dt),
-                                                 B, L, D, nl, 1 if mean_layers else 0, N.stream()),
-                "glr_wordpiece_segsum_bwd")
-        return (None, None) + tuple(dh.to(dt) for dt in dts)
-
-
-class WordpieceSegSumRowsFn(torch.autograd.Function):
-    """K5 on packed hidden states [T, D] (models/text_rows.py): token t of sentence b is row row_start[b] + t.  dst stays
-    [B, L], so word_emb / sent_emb are bitwise what the padded K5 gives; the backward writes the T packed rows."""
+    """K5: (token -> word-slot index [B, L], PackedRows or None, mean over the layers?, hidden states of the last layers)
+    -> word_emb [B, D, L], sent_emb [B, D].  rows=None: padded hidden states [B, L, D].  With a PackedRows they are [T, D]
+    (models/text_rows.py): token t of sentence b is row row_start[b] + t.  dst stays [B, L], so word_emb / sent_emb are
+    bitwise what the padded K5 gives; the backward writes the T packed rows."""
 
     @staticmethod
     def forward(ctx, dst, rows, mean_layers, *layers):
-        import ctypes
         hs = [h.detach().contiguous() for h in layers]
         if hs[0].dtype not in (torch.float32, torch.bfloat16):
             hs = [h.float() for h in hs]
-        T, D = hs[0].shape
-        B, L = rows.B, rows.L
-        if T != rows.T or tuple(dst.shape) != (B, L):
-            raise RuntimeError("WordpieceSegSumRowsFn: hidden states and dst do not match the row plan")
+        if rows is None:
+            B, L, D = hs[0].shape
+        else:
+            B, L, D = rows.B, rows.L, hs[0].shape[-1]
+            if tuple(hs[0].shape) != (rows.T, D) or tuple(dst.shape) != (B, L):
+                raise RuntimeError("WordpieceSegSumFn: hidden states and dst do not match the row plan")
         dev = hs[0].device
         word = torch.empty(B, D, L, dtype=torch.float32, device=dev)
         sent = torch.empty(B, D, dtype=torch.float32, device=dev)
         ptrs = (ctypes.c_void_p * len(hs))(*[h.data_ptr() for h in hs])
-        N.check(N.lib().glr_wordpiece_segsum_rows_fwd(ptrs, len(hs), N.dtype_code(hs[0].dtype), N.ptr(dst), N.ptr(rows.row_start),
-                                                      N.ptr(word), N.ptr(sent), B, L, D, 1 if mean_layers else 0, N.stream()),
-                "glr_wordpiece_segsum_rows_fwd")
+        fn, name, plan = _segsum(rows, "fwd")
+        N.check(fn(ptrs, len(hs), N.dtype_code(hs[0].dtype), N.ptr(dst), *plan, N.ptr(word), N.ptr(sent), B, L, D,
+                   1 if mean_layers else 0, N.stream()), name)
         ctx.save_for_backward(dst)
-        ctx.rows = rows
-        ctx.meta = (D, len(hs), mean_layers, [h.dtype for h in layers])
+        ctx.meta = (rows, hs[0].shape, B, L, D, len(hs), mean_layers, [h.dtype for h in layers])
         return word, sent
 
     @staticmethod
     def backward(ctx, d_word, d_sent):
         (dst,) = ctx.saved_tensors
-        rows = ctx.rows
-        D, nl, mean_layers, dts = ctx.meta
+        rows, shape, B, L, D, nl, mean_layers, dts = ctx.meta
         dw = None if d_word is None else d_word.float().contiguous()
         ds = None if d_sent is None else d_sent.float().contiguous()
         out_dt = torch.bfloat16 if dts[0] == torch.bfloat16 else torch.float32
-        dh = torch.empty(rows.T, D, dtype=out_dt, device=dst.device)
-        N.check(N.lib().glr_wordpiece_segsum_rows_bwd(N.ptr(dw), N.ptr(ds), N.ptr(dst), N.ptr(rows.row_start), N.ptr(dh),
-                                                      N.dtype_code(out_dt), rows.B, rows.L, D, nl, 1 if mean_layers else 0,
-                                                      N.stream()),
-                "glr_wordpiece_segsum_rows_bwd")
+        dh = torch.empty(shape, dtype=out_dt, device=dst.device)
+        fn, name, plan = _segsum(rows, "bwd")
+        N.check(fn(N.ptr(dw), N.ptr(ds), N.ptr(dst), *plan, N.ptr(dh), N.dtype_code(out_dt), B, L, D, nl,
+                   1 if mean_layers else 0, N.stream()), name)
         return (None, None, None) + tuple(dh.to(dt) for dt in dts)
+
+
+def _sum_word_pieces(embeddings, dst):
+    """embeddings [B, L, D] -> [B, L, D]: token t of sentence b added into word slot dst[b, t] (torch ops: CPU tensors)"""
+    B, L = dst.shape
+    flat = dst + (np.arange(B) * L)[:, None]
+    src = np.nonzero(dst.reshape(-1) >= 0)[0]
+    idx = torch.from_numpy(np.stack([src, flat.reshape(-1)[src]])).to(embeddings.device, non_blocking=True)
+    x = embeddings.reshape(B * L, -1)
+    return torch.zeros_like(x).index_add_(0, idx[1], x.index_select(0, idx[0])).view(B, L, -1)
 
 
 def host_ids(ids):
@@ -289,14 +269,6 @@ class BertEncoder(nn.Module):
         return (getattr(self, "_graph", None) is not None and self.training and torch.is_grad_enabled() and attn_mask is not None
                 and self._graph_key == (tuple(ids.shape), torch.get_autocast_dtype("cuda") if torch.is_autocast_enabled("cuda") else None))
 
-    def _encode(self, ids, attn_mask, token_type):
-        """hidden states of the last `last_n_layers` layers, through the captured graphs when they fit this call"""
-        if self._graph_fits(ids, attn_mask):
-            x = self.model.embeddings(ids, token_type)
-            self._graph_rng.refresh()
-            return self._graph(x, (attn_mask != 0)[:, None, None, :])
-        return None
-
     def _packed_rows(self, ids, attn_mask):
         """(PackedRows, word-piece slots) when this call may run the layers on its real token rows only, else (None, None):
         the K5 configuration on the GPU under bf16 autocast with every fused kernel on, host copies of ids and mask (no
@@ -314,9 +286,8 @@ class BertEncoder(nn.Module):
                 or tuple(np.shape(mask_h)) != tuple(ids.shape):
             return none
         c = self.model.config
-        ln = self.model.encoder.layer[0].output.LayerNorm
-        if (c.hidden_size != c.num_attention_heads * 64 or c.hidden_size % 256 != 0 or not 256 <= c.hidden_size <= 1024
-                or ln.weight.dtype != torch.float32):
+        if not (fused_attn.heads_ok(c.hidden_size, c.num_attention_heads)
+                and fused_ln.ln_ok(c.hidden_size, self.model.encoder.layer[0].output.LayerNorm)):
             return none
         slots = wordpiece_slots(np.asarray(ids_h), self.vocab)
         plan = text_rows.plan_rows(mask_h, slots[0], fused_attn._max_tokens())
@@ -327,58 +298,51 @@ class BertEncoder(nn.Module):
     def aggregate_tokens(self, embeddings, caption_ids):
         """embeddings [B, L, D] (already reduced over layers) -> word slots [B, L, D], sents."""
         ids = host_ids(caption_ids)
-        B, L = ids.shape
         dst, starts, n_words = wordpiece_slots(ids, self.vocab)
-        sents = SentenceBatch(ids, dst, starts, n_words, self.vocab, L)
-        flat = dst + (np.arange(B) * L)[:, None]
-        src = np.nonzero(dst.reshape(-1) >= 0)[0]
-        idx = torch.from_numpy(np.stack([src, flat.reshape(-1)[src]])).to(embeddings.device, non_blocking=True)
-        x = embeddings.reshape(B * L, -1)
-        out = torch.zeros_like(x).index_add_(0, idx[1], x.index_select(0, idx[0]))
-        return out.view(B, L, -1), sents
+        return _sum_word_pieces(embeddings, dst), SentenceBatch(ids, dst, starts, n_words, self.vocab, ids.shape[1])
+
+    def _hidden_states(self, ids, attn_mask, token_type):
+        """step 1, the route -> (hidden states of the last `last_n_layers` layers or None when only the last is read,
+        BertModel's outputs or None, PackedRows or None, the word-piece slots the row plan was made from or None)"""
+        rows, slots = self._packed_rows(ids, attn_mask)
+        if rows is not None:                    # the layers on the real token rows only; K5 reads the packed rows
+            x = self.model.embeddings(ids, token_type)
+            return encode_rows(self.model.encoder, x, rows, self.last_n_layers), None, rows, slots
+        if self.last_n_layers > 1 and self._graph_fits(ids, attn_mask):         # the captured graphs
+            x = self.model.embeddings(ids, token_type)
+            self._graph_rng.refresh()
+            return self._graph(x, (attn_mask != 0)[:, None, None, :]), None, None, None
+        outputs = self.model(ids, attn_mask, token_type)                        # padded, eager (and every CPU call)
+        return (outputs[2][-self.last_n_layers:] if self.last_n_layers > 1 else None), outputs, None, None
+
+    def _aggregate(self, ids, layers, outputs, rows, slots):
+        """step 2 -> (word_embeddings [B, L, D], sent_embeddings [B, D], sents)"""
+        if layers is not None and self.aggregate_method not in ("sum", "mean"):
+            print(self.aggregate_method)
+            raise Exception("Aggregation method not implemented")
+        host = host_ids(ids)
+        if layers is not None and self.agg_tokens:
+            dst, starts, n_words = wordpiece_slots(host, self.vocab) if slots is None else slots
+            sents = SentenceBatch(host, dst, starts, n_words, self.vocab, host.shape[1])
+        else:
+            dst, sents = None, [[self.vocab.tokens[int(w)] for w in sent] for sent in host]
+        if layers is None:
+            return outputs[0], outputs[1], sents
+        if dst is not None and layers[0].is_cuda:
+            # K5 (every GPU call, any D / layer count): segment-sum fused with the layer reduction and the L-mean,
+            # [B, D, L] written directly.  The torch branch below only ever sees CPU tensors (host-logic tests and the
+            # CPU baseline of bench.py).
+            dst_d = N.upload(dst.astype(np.int32), layers[0].device)
+            word, sent = WordpieceSegSumFn.apply(dst_d, rows, self.aggregate_method == "mean", *layers)
+            return word.permute(0, 2, 1), sent, sents                   # [B, L, D] view; permuted back in forward
+        word = torch.stack(layers).sum(0) if self.aggregate_method == "sum" else torch.stack(layers).mean(0)
+        if dst is not None:
+            word = _sum_word_pieces(word, dst)
+        return word, word.mean(dim=1), sents                            # over ALL L slots (ref :110)
 
     def forward(self, ids, attn_mask, token_type):
-        rows, slots = self._packed_rows(ids, attn_mask)
-        if rows is not None:                    # the layers on the real token rows only; K5 below reads the packed rows
-            layers = encode_rows(self.model.encoder, self.model.embeddings(ids, token_type), rows, self.last_n_layers)
-        else:
-            layers = self._encode(ids, attn_mask, token_type) if self.last_n_layers > 1 else None
-        outputs = self.model(ids, attn_mask, token_type) if layers is None else None
-        fused = None
-        if self.last_n_layers > 1:
-            if layers is None:
-                layers = outputs[2][-self.last_n_layers:]
-            if self.aggregate_method not in ("sum", "mean"):
-                print(self.aggregate_method)
-                raise Exception("Aggregation method not implemented")
-            if self.agg_tokens and layers[0].is_cuda:
-                # K5 (every GPU call, any D / layer count): segment-sum fused with the layer reduction and the
-                # L-mean, [B, D, L] written directly.  The torch branch below only ever sees CPU tensors (host-logic
-                # tests and the CPU baseline of bench.py).
-                host = host_ids(ids)
-                B, L = host.shape
-                dst, starts, n_words = wordpiece_slots(host, self.vocab) if slots is None else slots
-                sents = SentenceBatch(host, dst, starts, n_words, self.vocab, L)
-                dst_d = N.upload(dst.astype(np.int32), layers[0].device)
-                if rows is not None:
-                    fused = WordpieceSegSumRowsFn.apply(dst_d, rows, self.aggregate_method == "mean", *layers)
-                else:
-                    fused = WordpieceSegSumFn.apply(dst_d, self.aggregate_method == "mean", *layers)
-                word_embeddings = fused[0].permute(0, 2, 1)        # [B, L, D] view; permuted back below
-                sent_embeddings = fused[1]
-            else:
-                embeddings = torch.stack(layers).sum(0) if self.aggregate_method == "sum" else torch.stack(layers).mean(0)
-                if self.agg_tokens:
-                    word_embeddings, sents = self.aggregate_tokens(embeddings, ids)
-                else:
-                    word_embeddings = embeddings
-                    host = host_ids(ids)
-                    sents = [[self.vocab.tokens[int(w)] for w in sent] for sent in host]
-                sent_embeddings = word_embeddings.mean(dim=1)          # over ALL L slots (ref :110)
-        else:
-            word_embeddings, sent_embeddings = outputs[0], outputs[1]
-            host = host_ids(ids)
-            sents = [[self.vocab.tokens[int(w)] for w in sent] for sent in host]
+        layers, outputs, rows, slots = self._hidden_states(ids, attn_mask, token_type)
+        word_embeddings, sent_embeddings, sents = self._aggregate(ids, layers, outputs, rows, slots)
 
         batch_dim, num_words, feat_dim = word_embeddings.shape
         if self.emb_local is not None:

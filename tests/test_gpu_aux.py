@@ -38,7 +38,7 @@ def _k5(ids, hidden, vocab, grad=False):
     dst, starts, n_words = tm.wordpiece_slots(ids, v)
     layers = [torch.from_numpy(h).to(DEV).requires_grad_(grad) for h in hidden[-4:]]
     dst_d = torch.from_numpy(dst.astype(np.int32)).to(DEV)
-    word, sent = tm.WordpieceSegSumFn.apply(dst_d, False, *layers)
+    word, sent = tm.WordpieceSegSumFn.apply(dst_d, None, False, *layers)
     return word, sent, layers
 
 

@@ -415,7 +415,7 @@ def test_autograd_packed_equals_split_and_switch(monkeypatch):
         return a, b, qkv.grad, torch.cat((qs.grad, ks.grad, vs.grad), dim=-1), fus
     a, b, ga, gb, fus = both()
     assert fus
-    assert type(a.grad_fn).__name__ == "_SelfAttnPackedBackward" and type(b.grad_fn).__name__ == "_SelfAttnBackward"
+    assert type(a.grad_fn).__name__ == "_SelfAttnBackward" and type(b.grad_fn).__name__ == "_SelfAttnBackward"
     assert a.dtype == b.dtype == torch.bfloat16 and torch.isfinite(ga.float()).all() and float(ga.float().abs().sum()) > 0
     assert torch.equal(a.view(torch.int16), b.view(torch.int16))
     assert torch.equal(ga.view(torch.int16), gb.view(torch.int16))
