@@ -1791,6 +1791,7 @@ extern "C" int glr_local_attn_fwd(const void* vt, const void* gram, const void* 
   const int32_t* pair_tile = plan_dev + plan[GLR_PLAN_OFF_PAIR_TILE];
   const int32_t* pair_desc = plan_dev + plan[GLR_PLAN_OFF_PAIR_DESC];
   if (!sim || (attn && !attn_off)) return GLR_EINVAL;
+  if (img_offset < 0) return GLR_EINVAL;          // sent_slot0 / attn_off are indexed with img_offset + b
   if (pair_only && img_offset + B_img > p.n_sent) return GLR_EINVAL;
   if (!pair_only && n_single + n_pair == 0) return GLR_EINVAL;
   if (amean && pair_only) return GLR_EINVAL;

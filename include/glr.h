@@ -190,7 +190,7 @@ int glr_pack_words(const void* words_emb, int in_dtype, const int32_t* sent_slot
  *                strip = 1 drops the no-attention column (:60-61).  NULL = not wanted.
  *   pair_only    1: launch only the B_img diagonal (image b, tile of sentence img_offset+b) pairs;
  *                sim then only receives the diagonal entries (attention_fn, attention-finetune).
- *   img_offset   global index of local image 0 (data-parallel shard offset).
+ *   img_offset   global index of local image 0 (data-parallel shard offset), >= 0 (else GLR_EINVAL).
  *   amean        optional out fp32 [B_img, n_sent, S_pad]: the word-mean attention row of EVERY pair,
  *                A[b, i, r] = mean_w a2[b, i, w, r] (no-attention column at r = 0 when present, zeros for
  *                r >= S_eff) - the input of the attention regularisers (gloria_loss.py:129-139; K6
