@@ -19,6 +19,10 @@
 // * apply passes: short workgroups (256 threads x 4 vectors), and they walk the tensor in the OPPOSITE direction of the
 //   reduce pass in front of them, so the tail the reduce pass touched last is still in the 256 MB Infinity Cache.
 //
+// Global-batch statistics for data-parallel runs (glr_bn_sync_*): the same passes with the second stage cut in two where
+// the collective goes - k_bn_record writes this rank's channel sums as an fp64 record, the caller all-gathers the records,
+// k_bn_sync_finish adds them in rank order and forms the statistics with k_bn_finish's own device functions.
+//
 // Eval mode without autograd (validation, retrieval, zero-shot): glr_bn_infer is the apply pass alone with scale / shift
 // from the running statistics - one launch, 2E (3E), nothing written but y - and glr_bn_relu_maxpool3s2_infer folds
 // the stem's BatchNorm + ReLU into the max-pool's reads.
@@ -167,6 +171,46 @@ __device__ __forceinline__ double wave_sum(double v) {
   for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
   return v;
 }
+// the two stages of the second pass as device functions: the per-rank kernel (k_bn_finish) and the global-batch kernels
+// (k_bn_record / k_bn_sync_finish, the cross-rank boundary between them) run the SAME expressions, so that one record
+// (P = 1) is the per-rank computation by construction
+__device__ __forceinline__ void bn_part_sums(const float* __restrict__ part, int n_part, int C, int c, int lane, double& s,
+                                             double& ss) {
+  const float* p0 = part + (size_t)c * n_part;
+  const float* p1 = part + ((size_t)C + c) * n_part;
+  s = 0.0; ss = 0.0;
+  for (int k = lane; k < n_part; k += 64) { s += (double)p0[k]; ss += (double)p1[k]; }
+  s = wave_sum(s);
+  ss = wave_sum(ss);
+}
+// s = sum x, ss = sum x^2 over R rows -> mean / invstd (+ running statistics, momentum form of nn.BatchNorm2d)
+__device__ __forceinline__ void bn_fwd_stats(double s, double ss, long long R, float eps, float momentum, int c,
+                                             float* __restrict__ o0, float* __restrict__ o1, float* __restrict__ o2,
+                                             float* __restrict__ o3) {
+  const double m = s / (double)R;
+  double var = ss / (double)R - m * m;
+  if (var < 0.0) var = 0.0;
+  o0[c] = (float)m;                                        // mean
+  o1[c] = (float)(1.0 / sqrt(var + (double)eps));          // invstd
+  if (o2) {                                                // running mean / var
+    // two rounded products and a rounded sum: left to the compiler, one caller gets an fma here and the other does not
+#pragma clang fp contract(off)
+    const double unb = R > 1 ? var * (double)R / (double)(R - 1) : var;
+    o2[c] = (1.f - momentum) * o2[c] + momentum * (float)m;
+    o3[c] = (1.f - momentum) * o3[c] + momentum * (float)unb;
+  }
+}
+// (s_own, ss_own) = this rank's sum dz, sum dz xhat -> dgamma, dbeta; (s, ss) over the R rows of the whole batch -> the
+// two per-channel means of the dx formula.  Per-rank BatchNorm: own = whole.
+__device__ __forceinline__ void bn_bwd_stats(double s_own, double ss_own, double s, double ss, long long R, int c,
+                                             float* __restrict__ o0, float* __restrict__ o1, float* __restrict__ o2,
+                                             float* __restrict__ o3) {
+  o0[c] = (float)ss_own;                                   // dgamma
+  o1[c] = (float)s_own;                                    // dbeta
+  o2[c] = (float)(s / (double)R);                          // mean(dz)
+  o3[c] = (float)(ss / (double)R);                         // mean(dz xhat)
+}
+
 template <bool FWD>
 __global__ void __launch_bounds__(BN_NT) k_bn_finish(const float* __restrict__ part, int n_part, int C, long long R, float eps,
                                                      float momentum, float* __restrict__ o0, float* __restrict__ o1,
@@ -175,30 +219,61 @@ __global__ void __launch_bounds__(BN_NT) k_bn_finish(const float* __restrict__ p
   if (counter != nullptr && blockIdx.x == 0 && threadIdx.x == 0) counter[0] += 1;     // nn.BatchNorm2d.num_batches_tracked
   const int c = blockIdx.x * (BN_NT / 64) + (threadIdx.x >> 6);
   if (c >= C) return;
-  const float* p0 = part + (size_t)c * n_part;
-  const float* p1 = part + ((size_t)C + c) * n_part;
-  double s = 0.0, ss = 0.0;
-  for (int k = lane; k < n_part; k += 64) { s += (double)p0[k]; ss += (double)p1[k]; }
-  s = wave_sum(s);
-  ss = wave_sum(ss);
+  double s, ss;
+  bn_part_sums(part, n_part, C, c, lane, s, ss);
   if (lane != 0) return;
+  if (FWD)
+    bn_fwd_stats(s, ss, R, eps, momentum, c, o0, o1, o2, o3);
+  else
+    bn_bwd_stats(s, ss, s, ss, R, c, o0, o1, o2, o3);
+}
+
+// ---- global-batch BatchNorm (statistics over the rows of ALL ranks of a data-parallel run): the second stage is cut
+// where the collective goes.  k_bn_record ends a rank's own part - the channel sums in double, as a record the ranks
+// all-gather - and k_bn_sync_finish starts from the P records in rank order.
+//   forward  record double[2C + 1] = sum x [C] | sum x^2 [C] | (double) rows of this rank
+//   backward record double[2C]     = sum dz [C] | sum dz xhat [C]
+template <bool FWD>
+__global__ void __launch_bounds__(BN_NT) k_bn_record(const float* __restrict__ part, int n_part, int C, long long R,
+                                                     double* __restrict__ rec) {
+  const int lane = threadIdx.x & 63;
+  if (FWD && blockIdx.x == 0 && threadIdx.x == 0) rec[2 * (size_t)C] = (double)R;
+  const int c = blockIdx.x * (BN_NT / 64) + (threadIdx.x >> 6);
+  if (c >= C) return;
+  double s, ss;
+  bn_part_sums(part, n_part, C, c, lane, s, ss);
+  if (lane != 0) return;
+  rec[c] = s;
+  rec[(size_t)C + c] = ss;
+}
+
+// one wave per channel (k_bn_finish's grid); lane 0 adds the P records serially in rank order: every rank forms bitwise
+// the same totals from the same `recs`.  FWD writes the row count of the whole batch to `count`, BWD reads it there.
+template <bool FWD>
+__global__ void __launch_bounds__(BN_NT) k_bn_sync_finish(const double* __restrict__ recs, int P, int rank, int C, float eps,
+                                                          float momentum, float* __restrict__ o0, float* __restrict__ o1,
+                                                          float* __restrict__ o2, float* __restrict__ o3,
+                                                          long long* __restrict__ counter, long long* __restrict__ count) {
+  const size_t stride = 2 * (size_t)C + (FWD ? 1 : 0);
+  const int c = blockIdx.x * (BN_NT / 64) + (threadIdx.x >> 6);
+  if ((threadIdx.x & 63) != 0) return;
+  long long R = 0;
   if (FWD) {
-    const double m = s / (double)R;
-    double var = ss / (double)R - m * m;
-    if (var < 0.0) var = 0.0;
-    o0[c] = (float)m;                                        // mean
-    o1[c] = (float)(1.0 / sqrt(var + (double)eps));          // invstd
-    if (o2) {                                                // running mean / var
-      const double unb = R > 1 ? var * (double)R / (double)(R - 1) : var;
-      o2[c] = (1.f - momentum) * o2[c] + momentum * (float)m;
-      o3[c] = (1.f - momentum) * o3[c] + momentum * (float)unb;
+    for (int p = 0; p < P; ++p) R += (long long)recs[p * stride + 2 * (size_t)C];
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+      if (counter != nullptr) counter[0] += 1;             // nn.BatchNorm2d.num_batches_tracked: once per global batch
+      count[0] = R;
     }
   } else {
-    o0[c] = (float)ss;                                       // dgamma
-    o1[c] = (float)s;                                        // dbeta
-    o2[c] = (float)(s / (double)R);                          // mean(dz)
-    o3[c] = (float)(ss / (double)R);                         // mean(dz xhat)
+    R = count[0];
   }
+  if (c >= C) return;
+  double s = recs[c], ss = recs[(size_t)C + c];
+  for (int p = 1; p < P; ++p) { s += recs[p * stride + c]; ss += recs[p * stride + C + c]; }
+  if (FWD)
+    bn_fwd_stats(s, ss, R, eps, momentum, c, o0, o1, o2, o3);
+  else
+    bn_bwd_stats(recs[rank * stride + c], recs[rank * stride + C + c], s, ss, R, c, o0, o1, o2, o3);
 }
 
 // forward apply: y = relu?( (x - mean) invstd gamma + beta (+ residual) ); blocks walk the tensor backwards
@@ -376,11 +451,10 @@ extern "C" int glr_bn_workspace_floats(long long R, int C) {
   return bn_plan(R, C, BN_MAX_WG, 1).n_part * 2 * C;          // upper bound over both directions
 }
 
+// The launches of a site, one function per pass: the per-rank entry points chain reduce -> k_bn_finish -> apply, the
+// global-batch ones reduce -> k_bn_record | all-gather | k_bn_sync_finish -> apply.
 template <typename E>
-int bn_fwd_launch(const void* x, const void* residual, const float* gamma, const float* beta, long long R, int C, float eps,
-                  float momentum, int relu, float* run_mean, float* run_var, long long* num_batches_tracked, float* mean,
-                  float* invstd, float* workspace, void* y, hipStream_t st) {
-  constexpr int UNA = 4 >> ElemTraits<E>::SHIFT;
+int bn_fwd_reduce(const void* x, long long R, int C, float* workspace, int* n_part, hipStream_t st) {
   static GlrOccupancy occ0;
   const int res0 = bn_resident(occ0, (const void*)k_bn_reduce<E, 0, false>);
   const BnPlan pl = bn_plan(R, C, res0, 8 >> ElemTraits<E>::SHIFT);
@@ -388,9 +462,14 @@ int bn_fwd_launch(const void* x, const void* residual, const float* gamma, const
                      (const E*)nullptr, (const E*)nullptr, nullptr, nullptr, nullptr, nullptr, R, C, 0, pl.n_part, workspace,
                      (E*)nullptr, (const E*)nullptr);
   GLR_CHECK_LAUNCH();
-  hipLaunchKernelGGL((k_bn_finish<true>), dim3((C + 3) / 4), dim3(BN_NT), 0, st, workspace, pl.n_part, C, R, eps, momentum,
-                     mean, invstd, run_mean, run_var, num_batches_tracked);
-  GLR_CHECK_LAUNCH();
+  *n_part = pl.n_part;
+  return GLR_OK;
+}
+
+template <typename E>
+int bn_fwd_apply(const void* x, const void* residual, const float* gamma, const float* beta, const float* mean,
+                 const float* invstd, long long R, int C, int relu, void* y, hipStream_t st) {
+  constexpr int UNA = 4 >> ElemTraits<E>::SHIFT;
   const long long n_vec = R * C / 8;
   const int grid = (int)((n_vec + BN_NT * UNA - 1) / (BN_NT * UNA));
   if (residual)
@@ -404,10 +483,22 @@ int bn_fwd_launch(const void* x, const void* residual, const float* gamma, const
 }
 
 template <typename E>
-int bn_bwd_launch(const void* x, const void* dy, const void* dy2, const void* y, const float* gamma, const float* beta,
+int bn_fwd_launch(const void* x, const void* residual, const float* gamma, const float* beta, long long R, int C, float eps,
+                  float momentum, int relu, float* run_mean, float* run_var, long long* num_batches_tracked, float* mean,
+                  float* invstd, float* workspace, void* y, hipStream_t st) {
+  int n_part = 0;
+  const int rc = bn_fwd_reduce<E>(x, R, C, workspace, &n_part, st);
+  if (rc != GLR_OK) return rc;
+  hipLaunchKernelGGL((k_bn_finish<true>), dim3((C + 3) / 4), dim3(BN_NT), 0, st, workspace, n_part, C, R, eps, momentum,
+                     mean, invstd, run_mean, run_var, num_batches_tracked);
+  GLR_CHECK_LAUNCH();
+  return bn_fwd_apply<E>(x, residual, gamma, beta, mean, invstd, R, C, relu, y, st);
+}
+
+template <typename E>
+int bn_bwd_reduce(const void* x, const void* dy, const void* dy2, const void* y, const float* gamma, const float* beta,
                   const float* mean, const float* invstd, long long R, int C, int relu, int has_residual, float* workspace,
-                  float* out4c, void* dx, void* dres, hipStream_t st) {
-  constexpr int UNA = 4 >> ElemTraits<E>::SHIFT;
+                  void* dres, int* n_part, hipStream_t st) {
   static GlrOccupancy occ1, occ2;
   const int res1 = bn_resident(occ1, (const void*)k_bn_reduce<E, 1, false>);
   const int res2 = bn_resident(occ2, (const void*)k_bn_reduce<E, 1, true>);
@@ -421,19 +512,40 @@ int bn_bwd_launch(const void* x, const void* dy, const void* dy2, const void* y,
     hipLaunchKernelGGL((k_bn_reduce<E, 1, false>), rgrid, dim3(BN_NT), 0, st, (const E*)x, (const E*)dy,
                        (const E*)nullptr, mean, invstd, gamma, beta, R, C, relu, pl.n_part, workspace, (E*)nullptr, (const E*)nullptr);
   GLR_CHECK_LAUNCH();
-  hipLaunchKernelGGL((k_bn_finish<false>), dim3((C + 3) / 4), dim3(BN_NT), 0, st, workspace, pl.n_part, C, R, 0.f, 0.f, out4c,
-                     out4c + C, out4c + 2 * C, out4c + 3 * C, (long long*)nullptr);
-  GLR_CHECK_LAUNCH();
+  *n_part = pl.n_part;
+  return GLR_OK;
+}
+
+// dz: dy, or with a residual the dres the reduce pass wrote
+template <typename E>
+int bn_bwd_apply(const void* x, const void* dz, const float* gamma, const float* beta, const float* mean,
+                 const float* invstd, long long R, int C, int relu, int has_residual, const float* out4c, void* dx,
+                 hipStream_t st) {
+  constexpr int UNA = 4 >> ElemTraits<E>::SHIFT;
   const long long n_vec = R * C / 8;
   const int grid = (int)((n_vec + BN_NT * UNA - 1) / (BN_NT * UNA));
   if (has_residual)
-    hipLaunchKernelGGL((k_bn_bwd_apply<E, true>), dim3(grid), dim3(BN_NT), 0, st, (const E*)x, (const E*)dres,
+    hipLaunchKernelGGL((k_bn_bwd_apply<E, true>), dim3(grid), dim3(BN_NT), 0, st, (const E*)x, (const E*)dz,
                        mean, invstd, gamma, beta, out4c + 2 * C, out4c + 3 * C, n_vec, C, relu, (E*)dx);
   else
-    hipLaunchKernelGGL((k_bn_bwd_apply<E, false>), dim3(grid), dim3(BN_NT), 0, st, (const E*)x, (const E*)dy,
+    hipLaunchKernelGGL((k_bn_bwd_apply<E, false>), dim3(grid), dim3(BN_NT), 0, st, (const E*)x, (const E*)dz,
                        mean, invstd, gamma, beta, out4c + 2 * C, out4c + 3 * C, n_vec, C, relu, (E*)dx);
   GLR_CHECK_LAUNCH();
   return GLR_OK;
+}
+
+template <typename E>
+int bn_bwd_launch(const void* x, const void* dy, const void* dy2, const void* y, const float* gamma, const float* beta,
+                  const float* mean, const float* invstd, long long R, int C, int relu, int has_residual, float* workspace,
+                  float* out4c, void* dx, void* dres, hipStream_t st) {
+  int n_part = 0;
+  const int rc = bn_bwd_reduce<E>(x, dy, dy2, y, gamma, beta, mean, invstd, R, C, relu, has_residual, workspace, dres,
+                                  &n_part, st);
+  if (rc != GLR_OK) return rc;
+  hipLaunchKernelGGL((k_bn_finish<false>), dim3((C + 3) / 4), dim3(BN_NT), 0, st, workspace, n_part, C, R, 0.f, 0.f, out4c,
+                     out4c + C, out4c + 2 * C, out4c + 3 * C, (long long*)nullptr);
+  GLR_CHECK_LAUNCH();
+  return bn_bwd_apply<E>(x, has_residual ? dres : dy, gamma, beta, mean, invstd, R, C, relu, has_residual, out4c, dx, st);
 }
 
 extern "C" int glr_bn_act_fwd(const void* x, const void* residual, const float* gamma, const float* beta, long long R,
@@ -466,6 +578,73 @@ extern "C" int glr_bn_act_bwd(const void* x, const void* dy, const void* dy2, co
   if (dtype == GLR_F32)
     return bn_bwd_launch<float>(x, dy, dy2, y, gamma, beta, mean, invstd, R, C, relu, has_residual, workspace, out4c, dx, dres, st);
   return GLR_EDTYPE;
+}
+
+// ---- global-batch BatchNorm: each direction in two calls with the all-gather of the records between them
+extern "C" int glr_bn_sync_partial_fwd(const void* x, long long R, int C, float* workspace, double* rec, int dtype,
+                                       void* stream) {
+  if (!x || !workspace || !rec || !bn_shape_ok(R, C)) return GLR_EINVAL;
+  if (dtype != GLR_BF16 && dtype != GLR_F32) return GLR_EDTYPE;
+  hipStream_t st = (hipStream_t)stream;
+  int n_part = 0;
+  const int rc = dtype == GLR_BF16 ? bn_fwd_reduce<unsigned short>(x, R, C, workspace, &n_part, st)
+                                   : bn_fwd_reduce<float>(x, R, C, workspace, &n_part, st);
+  if (rc != GLR_OK) return rc;
+  hipLaunchKernelGGL((k_bn_record<true>), dim3((C + 3) / 4), dim3(BN_NT), 0, st, workspace, n_part, C, R, rec);
+  GLR_CHECK_LAUNCH();
+  return GLR_OK;
+}
+
+extern "C" int glr_bn_sync_apply_fwd(const void* x, const void* residual, const float* gamma, const float* beta,
+                                     const double* recs, int P, long long R, int C, float eps, float momentum, int relu,
+                                     float* run_mean, float* run_var, long long* num_batches_tracked, float* mean,
+                                     float* invstd, long long* count, void* y, int dtype, void* stream) {
+  if (!x || !gamma || !beta || !recs || P < 1 || !mean || !invstd || !count || !y || !bn_shape_ok(R, C)) return GLR_EINVAL;
+  if (dtype != GLR_BF16 && dtype != GLR_F32) return GLR_EDTYPE;
+  hipStream_t st = (hipStream_t)stream;
+  hipLaunchKernelGGL((k_bn_sync_finish<true>), dim3((C + 3) / 4), dim3(BN_NT), 0, st, recs, P, 0, C, eps, momentum, mean,
+                     invstd, run_mean, run_var, num_batches_tracked, count);
+  GLR_CHECK_LAUNCH();
+  if (dtype == GLR_BF16) return bn_fwd_apply<unsigned short>(x, residual, gamma, beta, mean, invstd, R, C, relu, y, st);
+  return bn_fwd_apply<float>(x, residual, gamma, beta, mean, invstd, R, C, relu, y, st);
+}
+
+extern "C" int glr_bn_sync_partial_bwd(const void* x, const void* dy, const void* dy2, const void* y, const float* gamma,
+                                       const float* beta, const float* mean, const float* invstd, long long R, int C,
+                                       int relu, int has_residual, float* workspace, double* rec, void* dres, int dtype,
+                                       void* stream) {
+  if (!x || !dy || !gamma || !beta || !mean || !invstd || !workspace || !rec || !bn_shape_ok(R, C) ||
+      (has_residual && (!y || !dres)) || (dy2 && !has_residual))
+    return GLR_EINVAL;
+  if (dtype != GLR_BF16 && dtype != GLR_F32) return GLR_EDTYPE;
+  hipStream_t st = (hipStream_t)stream;
+  int n_part = 0;
+  const int rc = dtype == GLR_BF16
+                     ? bn_bwd_reduce<unsigned short>(x, dy, dy2, y, gamma, beta, mean, invstd, R, C, relu, has_residual,
+                                                     workspace, dres, &n_part, st)
+                     : bn_bwd_reduce<float>(x, dy, dy2, y, gamma, beta, mean, invstd, R, C, relu, has_residual, workspace,
+                                            dres, &n_part, st);
+  if (rc != GLR_OK) return rc;
+  hipLaunchKernelGGL((k_bn_record<false>), dim3((C + 3) / 4), dim3(BN_NT), 0, st, workspace, n_part, C, R, rec);
+  GLR_CHECK_LAUNCH();
+  return GLR_OK;
+}
+
+extern "C" int glr_bn_sync_apply_bwd(const void* x, const void* dz, const float* gamma, const float* beta, const float* mean,
+                                     const float* invstd, const double* recs, int P, int rank, const long long* count,
+                                     long long R, int C, int relu, int has_residual, float* out4c, void* dx, int dtype,
+                                     void* stream) {
+  if (!x || !dz || !gamma || !beta || !mean || !invstd || !recs || P < 1 || rank < 0 || rank >= P || !count || !out4c ||
+      !dx || !bn_shape_ok(R, C))
+    return GLR_EINVAL;
+  if (dtype != GLR_BF16 && dtype != GLR_F32) return GLR_EDTYPE;
+  hipStream_t st = (hipStream_t)stream;
+  hipLaunchKernelGGL((k_bn_sync_finish<false>), dim3((C + 3) / 4), dim3(BN_NT), 0, st, recs, P, rank, C, 0.f, 0.f, out4c,
+                     out4c + C, out4c + 2 * C, out4c + 3 * C, (long long*)nullptr, const_cast<long long*>(count));
+  GLR_CHECK_LAUNCH();
+  if (dtype == GLR_BF16)
+    return bn_bwd_apply<unsigned short>(x, dz, gamma, beta, mean, invstd, R, C, relu, has_residual, out4c, dx, st);
+  return bn_bwd_apply<float>(x, dz, gamma, beta, mean, invstd, R, C, relu, has_residual, out4c, dx, st);
 }
 
 template <typename E>

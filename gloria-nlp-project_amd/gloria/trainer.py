@@ -32,6 +32,17 @@ class Trainer:
         # data-parallel parity mode: BatchNorm statistics over the GLOBAL batch (torch SyncBatchNorm: one small
         # per-channel all-reduce per layer) - the reference oracle is single-device full-batch BN (SURVEY.md
         # section 7); the default keeps per-rank statistics (speed mode)
+        # sync_bn="fused" (opt-in): the same statistics on the project's own BatchNorm kernels - one all-gather of
+        # 2C+1 doubles per site and direction between their two passes (gloria/models/fused_bn.py: GlobalBatchNorm2d).
+        # With the kernels switched off (GLR_FUSED_BN=0) it is sync_bn=True.
+        if isinstance(sync_bn, str) and sync_bn != "fused":
+            raise ValueError(f"sync_bn must be False, True or 'fused', got {sync_bn!r}")
+        if isinstance(sync_bn, str):
+            from .models import fused_bn
+            if not fused_bn.ENABLED:
+                print("Trainer: sync_bn='fused' needs the fused BatchNorm kernels (GLR_FUSED_BN=0): using torch SyncBatchNorm")
+                sync_bn = True
+        self.sync_bn_fused = sync_bn == "fused"
         self.sync_bn = bool(sync_bn)
         # hipGraph capture of both encoders' forward + backward at the first training step (GLoRIA.enable_image_graph: the
         # whole image encoder; BertEncoder.enable_graph: the 12 BERT layers): small per-rank batches are bound by the HOST
@@ -83,7 +94,12 @@ class Trainer:
             torch.backends.cudnn.benchmark = bool(self.miopen_benchmark)
             model.gloria.img_encoder.to(memory_format=torch.channels_last)
         model.gloria.dist = self.dist
-        if self.sync_bn and self.dist is not None and self.dist.world_size > 1:
+        if self.sync_bn_fused:
+            # every active data-parallel context, the single-rank rehearsal (GLR_FORCE_DIST=1) included
+            if self.dist is not None and self.dist.active:
+                from .models.fused_bn import convert_global_batchnorm
+                model.gloria.img_encoder = convert_global_batchnorm(model.gloria.img_encoder, self.dist)
+        elif self.sync_bn and self.dist is not None and self.dist.world_size > 1:
             model.gloria.img_encoder = torch.nn.SyncBatchNorm.convert_sync_batchnorm(model.gloria.img_encoder,
                                                                                       self.dist.group)
         # how build_optimizer is to build the optimizer for THIS run, written explicitly in both cases: the cfg also

@@ -394,6 +394,38 @@ int glr_bn_act_bwd(const void* x, const void* dy, const void* dy2, const void* y
                    const float* invstd, long long R, int C, int relu, int has_residual, float* workspace, float* out4c,
                    void* dx, void* dres, int dtype, void* stream);
 
+/* Global-batch BatchNorm for data-parallel runs: the passes of glr_bn_act_fwd / glr_bn_act_bwd with the cross-rank
+ * boundary in the middle.  Each direction is two calls; between them the caller all-gathers one small record per rank
+ * (fp64, device memory) and hands the P records back in rank order.  Shapes, element types and the workspace are those of
+ * glr_bn_act_fwd / glr_bn_act_bwd; R is THIS rank's row count (ranks may differ).
+ *   glr_bn_sync_partial_fwd  statistics pass over x; rec double[2C + 1] = sum x [C] | sum x^2 [C] | (double) R
+ *   glr_bn_sync_apply_fwd    recs double[P][2C + 1].  Totals over the P records, added serially in rank order in double;
+ *                            R_total = sum of the counts; mean, invstd [C] out (statistics of the whole batch, the
+ *                            expressions of glr_bn_act_fwd); run_mean / run_var (NULL = none) updated with the unbiased
+ *                            variance over R_total rows, num_batches_tracked (NULL = none) incremented once; count (int64
+ *                            device scalar) = R_total for the backward; then y like glr_bn_act_fwd.  Every rank computes
+ *                            bitwise the same mean, invstd and buffers from the same recs.
+ *   glr_bn_sync_partial_bwd  reduce pass like glr_bn_act_bwd (with a residual: y gives the ReLU mask, dres is written,
+ *                            dy2 is added while read); rec double[2C] = sum dz [C] | sum dz xhat [C]
+ *   glr_bn_sync_apply_bwd    recs double[P][2C]; dz = dy, or with a residual the dres of the partial call.
+ *                            out4c = [dgamma | dbeta | 2C floats of scratch]: dgamma / dbeta are THIS rank's sums
+ *                            (recs[rank]; the caller SUM-reduces parameter gradients over the ranks like any other), the
+ *                            two means of the dx formula are the rank-ordered totals / count[0]; then dx.
+ * One record (P = 1, rank = 0) is glr_bn_act_fwd / glr_bn_act_bwd bitwise: the same device functions sum the partials and
+ * form the statistics.  No atomics; every order of summation is fixed.
+ */
+int glr_bn_sync_partial_fwd(const void* x, long long R, int C, float* workspace, double* rec, int dtype, void* stream);
+int glr_bn_sync_apply_fwd(const void* x, const void* residual, const float* gamma, const float* beta, const double* recs,
+                          int P, long long R, int C, float eps, float momentum, int relu, float* run_mean, float* run_var,
+                          long long* num_batches_tracked, float* mean, float* invstd, long long* count, void* y, int dtype,
+                          void* stream);
+int glr_bn_sync_partial_bwd(const void* x, const void* dy, const void* dy2, const void* y, const float* gamma,
+                            const float* beta, const float* mean, const float* invstd, long long R, int C, int relu,
+                            int has_residual, float* workspace, double* rec, void* dres, int dtype, void* stream);
+int glr_bn_sync_apply_bwd(const void* x, const void* dz, const float* gamma, const float* beta, const float* mean,
+                          const float* invstd, const double* recs, int P, int rank, const long long* count, long long R,
+                          int C, int relu, int has_residual, float* out4c, void* dx, int dtype, void* stream);
+
 /* Eval-mode BatchNorm2d (+ residual add) (+ ReLU) without autograd: the same 53 sites when the image encoder runs under
  * model.eval() and torch.no_grad() (Trainer.evaluate, get_similarities, zero-shot, retrieval).  ONE launch per site: no
  * statistics, no workspace; nothing but y is written (the running buffers are inputs).  Per channel, in fp32,
