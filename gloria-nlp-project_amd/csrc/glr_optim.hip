@@ -15,6 +15,7 @@
 // GradScaler's skip of native AMP, decided on the device with no host round trip.  The unguarded instantiations are
 // the code of the plain entry points, unchanged.
 #include <climits>
+#include <cmath>
 
 #include "glr_common.h"
 
@@ -342,7 +343,64 @@ __global__ void __launch_bounds__(OPT_NT) k_gather_mt(const ChunkEnt* __restrict
   }
 }
 
+// accumulate: acc[foff + i] = scale * g (FIRST: the slot's old content is never read, a parameter without a gradient is
+// written with zeros) or fmaf(scale, g, acc[foff + i]) (a parameter without a gradient keeps its slot) - one rounding
+// per element either way, g the bf16 / fp32 gradient widened to fp32.  Only [foff, foff + count) is written: the padding
+// between parameters keeps its zeros.  HBM-bound: 2 (4) + 4 bytes read, 4 written per element; FIRST saves the 4.
+template <bool FIRST>
+__global__ void __launch_bounds__(OPT_NT) k_accum_mt(const ChunkEnt* __restrict__ chunk, const unsigned long long* __restrict__ gptr,
+                                                     int dtype, float* __restrict__ acc, float scale) {
+  const ChunkEnt e = chunk[blockIdx.x];
+  const void* g = reinterpret_cast<const void*>(gptr[e.param]);
+  if (g == nullptr && !FIRST) return;
+  float* dst = acc + e.foff;
+  const int nv = e.count & ~7;
+  // chunks start 8-aligned in the accumulator and inside the parameter: 16-byte accesses up to nv, scalars after it
+  for (int i = threadIdx.x * OPT_VEC; i < nv; i += OPT_NT * OPT_VEC) {
+    float v[8];
+    if (g != nullptr) {
+      load8(g, dtype, (size_t)e.poff + i, v);
+      if constexpr (FIRST) {
+#pragma unroll
+        for (int k = 0; k < 8; ++k) v[k] = scale * v[k];
+      } else {
+        float a[8];
+        load8(dst, GLR_F32, (size_t)i, a);
+#pragma unroll
+        for (int k = 0; k < 8; ++k) v[k] = __builtin_fmaf(scale, v[k], a[k]);
+      }
+    } else {
+#pragma unroll
+      for (int k = 0; k < 8; ++k) v[k] = 0.f;
+    }
+    *reinterpret_cast<float4*>(dst + i) = make_float4(v[0], v[1], v[2], v[3]);
+    *reinterpret_cast<float4*>(dst + i + 4) = make_float4(v[4], v[5], v[6], v[7]);
+  }
+  for (int i = nv + threadIdx.x; i < e.count; i += OPT_NT) {
+    float x = 0.f;
+    if (g != nullptr) {
+      x = ld1(g, dtype, (size_t)e.poff + i);
+      x = FIRST ? scale * x : __builtin_fmaf(scale, x, dst[i]);
+    }
+    dst[i] = x;
+  }
+}
+
 }  // namespace
+
+extern "C" int glr_accum_mt(const void* chunk_table, int n_chunks, const uint64_t* grad_ptrs, int src_dtype, float* acc,
+                            float scale, int first, void* stream) {
+  if (!chunk_table || !grad_ptrs || !acc || n_chunks <= 0 || !std::isfinite(scale)) return GLR_EINVAL;
+  if (src_dtype != GLR_F32 && src_dtype != GLR_BF16) return GLR_EDTYPE;
+  if (first)
+    hipLaunchKernelGGL(k_accum_mt<true>, dim3(n_chunks), dim3(OPT_NT), 0, (hipStream_t)stream, (const ChunkEnt*)chunk_table,
+                       (const unsigned long long*)grad_ptrs, src_dtype, acc, scale);
+  else
+    hipLaunchKernelGGL(k_accum_mt<false>, dim3(n_chunks), dim3(OPT_NT), 0, (hipStream_t)stream, (const ChunkEnt*)chunk_table,
+                       (const unsigned long long*)grad_ptrs, src_dtype, acc, scale);
+  GLR_CHECK_LAUNCH();
+  return GLR_OK;
+}
 
 extern "C" int glr_gather_mt(const void* chunk_table, int n_chunks, const uint64_t* grad_ptrs, int dtype, void* flat,
                              void* stream) {

@@ -44,6 +44,7 @@ SYMBOLS = {
                                    # xout, aout, baout, gamma, beta, a1buf, dtype, stream
     "glr_sumsq_blocks": (c_int, [ctypes.c_longlong]),
     "glr_gather_mt": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p]),
+    "glr_accum_mt": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_float, c_int, c_void_p]),
     "glr_sumsq_mt": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p]),
     "glr_adam_step_mt": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_float,
                                  c_float, c_float, c_float, c_int, c_void_p, c_void_p]),

@@ -93,7 +93,8 @@ def build_optimizer(cfg, lr, model):
         params = [p for p in params if id(p) not in skip]
         return ShadowAdam(params, all_params=all_params, lr=lr, betas=(0.5, 0.999), weight_decay=float(cfg.train.optimizer.weight_decay),
                           max_grad_norm=cfg.train.optimizer.flat_clip, shadow_ids=shadow_parameter_ids(model),
-                          flat_grads=bool(cfg.train.optimizer.flat_grads))
+                          flat_grads=bool(cfg.train.optimizer.flat_grads),
+                          accumulate=int(cfg.train.optimizer.flat_accumulate or 1))
 
     if cfg.train.optimizer.name == "SGD":
         return torch.optim.SGD(params, lr=lr, momentum=cfg.momentum, weight_decay=cfg.weight_decay)

@@ -77,7 +77,8 @@ def pretrain_config(name="imagenome", batch_size=48, **overrides):
         "phase": "pretrain",
         "random_seed": 0,
         "lightning": {"trainer": {"gpus": "0", "max_epochs": 50, "distributed_backend": "dp",
-                                  "gradient_clip_val": 0.25, "lr": 0.00005, "precision": 16}},
+                                  "gradient_clip_val": 0.25, "lr": 0.00005, "precision": 16,
+                                  "accumulate_grad_batches": None}},
         "model": {
             "gloria": {"local_loss_weight": 1.0, "global_loss_weight": 1.0, "temp1": 4.0, "temp2": 5.0,
                        "temp3": 10.0, "no_attn_vec": False},

@@ -130,7 +130,13 @@ class GradReducer:
     buckets of `bucket_bytes`; every `.grad` is a VIEW into its bucket, so nothing is copied in or out.
     A post-accumulate hook counts ready gradients; when a bucket is complete its SUM all-reduce is
     launched asynchronously on the collective stream while backward keeps running.  `finish()` waits for
-    all buckets.  xGMI is point-to-point: few large buckets (64 MiB) keep RCCL on all links."""
+    all buckets.  xGMI is point-to-point: few large buckets (64 MiB) keep RCCL on all links.
+
+    Gradient accumulation: a cycle stays ONE backward between its opening call and `finish()`; `begin(first, last)`
+    opens a cycle and says where in a window of micro-batches it lies (`zero_grad()` is `begin(True, True)`, a window of
+    one).  Gradients are summed locally over the cycles of a window - autograd adds in place into the bucket views, or,
+    for a flat optimizer built with accumulate > 1, `group.accumulate` adds each bucket into the fp32 flat accumulator -
+    and all-reduced once, in the window's last cycle."""
 
     @classmethod
     def from_flat(cls, groups, ctx, bucket_bytes=64 << 20, overlap=True):
@@ -166,6 +172,7 @@ class GradReducer:
         self._done = [False] * len(self.buckets)
         self._streams = {}
         self._open = False
+        self._first, self._last, self._scale, self._used = True, True, 1.0, set()
         return self
 
     def _join_streams(self, i):
@@ -193,10 +200,15 @@ class GradReducer:
         self._join_streams(i)
         if getattr(self, "_flat", None):
             g, i0, i1 = self._flat[i]
-            buf = g.gather(i0, i1)
+            if g.accum > 1:               # the flat buffer is never zeroed: `first` rewrites it in the kernel
+                buf = g.accumulate(i0, i1, self._scale, self._first)
+            else:
+                buf = g.gather(i0, i1)
             self._done[i] = True
         else:
             buf = self.buckets[i][0]
+        if not self._last:                # the window's sum is all-reduced once, by its last cycle
+            return
         self._pending.append(dist.all_reduce(buf, group=self.ctx.group, async_op=True))
 
     def __init__(self, params, ctx, bucket_bytes=64 << 20):
@@ -217,7 +229,9 @@ class GradReducer:
         self._pending = []
         self._ready = [0] * len(self.buckets)
         self._streams = {}                # bucket -> {stream handle: (stream, [params])} of the current cycle
-        self._open = False                # a zero_grad() .. finish() cycle is in progress
+        self._open = False                # a zero_grad() / begin() .. finish() cycle is in progress
+        self._first, self._last, self._scale = True, True, 1.0     # the current cycle's place in its window
+        self._used = set()                # params whose gradient arrived in any cycle of the current window
 
     def _seal(self, plist):
         dev, dt = plist[0].device, plist[0].dtype
@@ -237,17 +251,29 @@ class GradReducer:
         self.buckets.append((flat, plist))
 
     def zero_grad(self):
+        self.begin(True, True)
+
+    def begin(self, first=True, last=True, scale=1.0):
+        """open a cycle: `first` / `last` micro-batch of its accumulation window (both: no accumulation).  `scale`
+        multiplies the gradients on their way into a flat optimizer's accumulator (1 / k); the stock reducer's caller
+        scales the loss instead."""
+        self._first, self._last, self._scale = bool(first), bool(last), float(scale)
         if getattr(self, "_flat", None):
             for g in {id(f[0]): f[0] for f in self._flat}.values():
-                g.grad.zero_()
+                if g.accum == 1:
+                    if not (first and last):
+                        raise RuntimeError("GradReducer: accumulation over a flat optimizer needs ShadowAdam(accumulate > 1)")
+                    g.grad.zero_()
                 for p in g.params:
                     p.grad = None
             self._done = [False] * len(self.buckets)
-        else:
+        elif first:
             for flat, plist in self.buckets:
                 flat.zero_()
                 for p in plist:
                     p.grad = self._views[p]       # re-attach: finish() hides the views of unused parameters
+        if first:
+            self._used = set()
         self._ready = [0] * len(self.buckets)
         self._pending = []
         self._fired = set()
@@ -259,6 +285,7 @@ class GradReducer:
             # a bucket may only be reduced once per cycle: a second backward would all-reduce already reduced sums
             raise RuntimeError("GradReducer: one backward per zero_grad()/finish() cycle (no gradient accumulation)")
         self._fired.add(p)
+        self._used.add(p)
         self._ready[i] += 1
         if p.is_cuda:
             # which stream produced this gradient (plain-int handle: ~0.3 us per hook)
@@ -282,11 +309,12 @@ class GradReducer:
         self._open = False
         # a parameter no rank used (e.g. the BERT pooler with last_n_layers > 1) must look to the optimizer as it
         # does in the single-process run - grad None, skipped - not as a zero gradient that weight decay acts on
-        if not self._hide_unused:
+        # ("unused" is decided over the whole window, when it closes)
+        if not self._hide_unused or not self._last:
             return
         for _, plist in self.buckets:
             for p in plist:
-                if p not in self._fired:
+                if p not in self._used:
                     p.grad = None
 
 

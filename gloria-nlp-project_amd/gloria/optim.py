@@ -41,8 +41,8 @@ CHUNK = 16384          # elements per workgroup of the pointer-table kernels
 
 
 class _Group:
-    def __init__(self, params, shadow, device, flat_grads):
-        self.params, self.shadow, self.flat_grads = params, shadow, flat_grads
+    def __init__(self, params, shadow, device, flat_grads, accumulate=1):
+        self.params, self.shadow, self.flat_grads, self.accum = params, shadow, flat_grads, int(accumulate)
         self.offsets, off = [], 0
         for p in params:
             self.offsets.append(off)
@@ -52,7 +52,12 @@ class _Group:
         self.master = torch.zeros(self.n, **f32)
         self.exp_avg = torch.zeros(self.n, **f32)
         self.exp_avg_sq = torch.zeros(self.n, **f32)
-        self.gdt = torch.bfloat16 if shadow else torch.float32
+        # sdt: the dtype of the gradients autograd hands over (the parameter dtype); gdt: the dtype of the flat gradient
+        # buffer - the same, except that a buffer that accumulates micro-batches is fp32 in every group (a bf16 buffer
+        # would sum them at 8 bits of mantissa).  The accumulator is allocated once, zeroed, and its padding between
+        # parameters is never written again.
+        self.sdt = torch.bfloat16 if shadow else torch.float32
+        self.gdt = torch.float32 if self.accum > 1 else self.sdt
         self.grad = torch.zeros(self.n, dtype=self.gdt, device=device) if flat_grads else None
         self.shadow_buf = torch.zeros(self.n, dtype=torch.bfloat16, device=device) if shadow else None
         for p, o in zip(params, self.offsets):
@@ -88,7 +93,7 @@ class _Group:
         self._keep = []
 
     def stage_grad_pointers(self, i0=0, i1=None):
-        """addresses of this step's gradients of parameters [i0, i1) (dense, parameter strides, group dtype) -> device"""
+        """addresses of this step's gradients of parameters [i0, i1) (dense, parameter strides, source dtype) -> device"""
         i1 = len(self.params) if i1 is None else i1
         st = self.ptr_stage.get(i0)
         if st is None:
@@ -97,7 +102,7 @@ class _Group:
             st[1].synchronize()                       # the upload that last used this staging buffer has run
         host = st[0]
         keep, ptrs = [], []
-        gdt = self.gdt
+        gdt = self.sdt
         for p in self.params[i0:i1]:
             g = p.grad
             if g is None:
@@ -127,16 +132,37 @@ class _Group:
         end = self.offsets[i1] if i1 < len(self.params) else self.n
         return self.grad[self.offsets[i0]:end]
 
+    def accumulate(self, i0, i1, scale, first):
+        """gradient accumulation (accumulate > 1): scale x the gradients of parameters [i0, i1) -> their slots of the
+        fp32 flat accumulator, written (`first`: the window's first micro-batch, nothing is read or zeroed beforehand) or
+        added (one glr_accum_mt launch), then released; returns the slice of the accumulator that holds them"""
+        self.stage_grad_pointers(i0, i1)
+        c0, c1 = self.chunk_start[i0], self.chunk_start[i1]
+        rec = 24                          # bytes per chunk-table entry
+        N.check(N.lib().glr_accum_mt(N.ptr(self.table[c0 * rec:]), c1 - c0, N.ptr(self.ptr_dev), N.dtype_code(self.sdt),
+                                     N.ptr(self.grad), float(scale), int(bool(first)), N.stream()), "glr_accum_mt")
+        for i in range(i0, i1):
+            self.params[i].grad = None
+        end = self.offsets[i1] if i1 < len(self.params) else self.n
+        return self.grad[self.offsets[i0]:end]
+
     def view(self, buf, i):
         p, o = self.params[i], self.offsets[i]
         return buf.as_strided(p.shape, p.stride(), storage_offset=o)
 
 
 class ShadowAdam(torch.optim.Optimizer):
-    """Adam (torch semantics) over flat buffers.  `shadow_ids`: ids of the parameters that become bf16 shadows."""
+    """Adam (torch semantics) over flat buffers.  `shadow_ids`: ids of the parameters that become bf16 shadows.
+
+    accumulate=k > 1 (gradient accumulation over windows of k micro-batches): every group gets an fp32 flat gradient
+    buffer, `accumulate(scale, first)` (or the data-parallel reducer, bucket by bucket) adds each micro-batch's gradients
+    into it with one launch per group, and step() - called once per window - reads that buffer with the flat kernels.
+    An accumulating run therefore has the flat-buffer semantics of a data-parallel run, in a single process too: a
+    parameter that received no gradient in the whole window reads as a ZERO gradient (weight decay and the moments'
+    decay act on it) instead of being skipped.  The accumulator is not part of the checkpoint."""
 
     def __init__(self, params, lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, max_grad_norm=None, shadow_ids=(),
-                 flat_grads=False, all_params=None):
+                 flat_grads=False, all_params=None, accumulate=1):
         """Gradients always stay where autograd puts them (one tensor per parameter: making `.grad` a view of a flat
         buffer costs an accumulation launch per parameter).  flat_grads=False (single process): the norm / Adam kernels
         read them through a pointer table.  flat_grads=True (data parallel): the reducer gathers every bucket's
@@ -163,8 +189,11 @@ class ShadowAdam(torch.optim.Optimizer):
         # reverse registration order: backward produces gradients roughly back to front, so consecutive ranges of a
         # flat buffer complete together (the reducer's buckets)
         rev = list(reversed(params))
-        self.flat_grads = bool(flat_grads)
-        self.groups = [_Group(pl, sh, dev, self.flat_grads)
+        if isinstance(accumulate, bool) or not isinstance(accumulate, int) or accumulate < 1:
+            raise ValueError(f"ShadowAdam: accumulate must be an integer >= 1, got {accumulate!r}")
+        self.accum = accumulate
+        self.flat_grads = bool(flat_grads) or accumulate > 1     # which kernels step() runs: the flat forms
+        self.groups = [_Group(pl, sh, dev, self.flat_grads, accumulate)
                        for pl, sh in (([p for p in rev if id(p) in shadow_ids], True),
                                       ([p for p in rev if id(p) not in shadow_ids], False)) if pl]
         self.max_grad_norm = float(max_grad_norm) if max_grad_norm else 0.0
@@ -176,7 +205,8 @@ class ShadowAdam(torch.optim.Optimizer):
         # the guard's record (include/glr.h GLR_GUARD_*): applied steps (Adam's t - the truth), skip counters, the first
         # non-finite element of the last skipped step
         self.record = torch.zeros(NF.RECORD_WORDS, dtype=torch.int64, device=dev)
-        self.calls = 0                           # step() calls: the call index the guard notes for a skipped step
+        self.calls = 0                           # step() calls (= optimizer steps, one per accumulation window): the
+        #                                          call index the guard notes for a skipped step
         self._bias, self._bias_cap, self._bias_betas = None, 0, None
         # where each partial sum comes from (host only: NF.locate)
         self.layout = [NF.group_layout([p.numel() for p in g.params], nblocks=nb if self.flat_grads else None,
@@ -189,10 +219,19 @@ class ShadowAdam(torch.optim.Optimizer):
     # ---------------------------------------------------------------- one step
     def zero_grad(self, set_to_none=False):
         for g in self.groups:
-            if self.flat_grads:
+            if self.flat_grads and self.accum == 1:
                 g.grad.zero_()            # slots of parameters without a gradient (and the padding) read as zero
-            for p in g.params:
+            for p in g.params:            # (an accumulator is rewritten by its window's first accumulate())
                 p.grad = None
+
+    @torch.no_grad()
+    def accumulate(self, scale, first):
+        """one micro-batch of a window (accumulate > 1): scale x every parameter's gradient into the fp32 flat
+        accumulators, one launch per group; `first` starts a new window"""
+        if self.accum == 1:
+            raise RuntimeError("ShadowAdam.accumulate needs an optimizer built with accumulate > 1")
+        for g in self.groups:
+            g.accumulate(0, len(g.params), scale, first)
 
     def _bias_table(self, b1, b2):
         """device table of Adam's bias corrections for steps 1 .. capacity (glr_adam_bias_table: the host expressions of
@@ -220,7 +259,7 @@ class ShadowAdam(torch.optim.Optimizer):
                                               N.ptr(self._nonfinite[2 * o:]), st), "glr_sumsq_partial_g")
             else:
                 g.stage_grad_pointers()
-                N.check(L.glr_sumsq_mt_g(N.ptr(g.table), g.n_chunks, N.ptr(g.ptr_dev), N.dtype_code(g.gdt),
+                N.check(L.glr_sumsq_mt_g(N.ptr(g.table), g.n_chunks, N.ptr(g.ptr_dev), N.dtype_code(g.sdt),
                                          N.ptr(self._partial[o:]), N.ptr(self._nonfinite[2 * o:]), st), "glr_sumsq_mt_g")
             o += nb
         N.check(L.glr_step_guard(N.ptr(self._partial), N.ptr(self._nonfinite), o, self.max_grad_norm,
@@ -235,7 +274,7 @@ class ShadowAdam(torch.optim.Optimizer):
                 N.check(L.glr_adam_step_g(N.ptr(g.master), N.ptr(g.exp_avg), N.ptr(g.exp_avg_sq), N.ptr(g.grad),
                                           N.dtype_code(g.gdt), N.ptr(g.shadow_buf), g.n, *hyper), "glr_adam_step_g")
             else:
-                N.check(L.glr_adam_step_mt_g(N.ptr(g.table), g.n_chunks, N.ptr(g.ptr_dev), N.dtype_code(g.gdt),
+                N.check(L.glr_adam_step_mt_g(N.ptr(g.table), g.n_chunks, N.ptr(g.ptr_dev), N.dtype_code(g.sdt),
                                              N.ptr(g.master), N.ptr(g.exp_avg), N.ptr(g.exp_avg_sq), N.ptr(g.shadow_buf),
                                              *hyper), "glr_adam_step_mt_g")
 

@@ -2,7 +2,14 @@
 run.py:172-207 (precision 16 -> bf16 autocast here, gradient_clip_val 0.25, Adam(0.5, 0.999),
 ReduceLROnPlateau, ModelCheckpoint-style save/resume with the reference's checkpoint layout).
 One process per GPU; with a DistContext the loss is the global-batch loss and parameter gradients
-are SUM-all-reduced before clipping (so the clip uses the global norm)."""
+are SUM-all-reduced before clipping (so the clip uses the global norm).
+
+Gradient accumulation (Lightning's `accumulate_grad_batches`, 1.1.4 semantics): a window is k consecutive training
+batches, each a full forward and backward of its own; the optimizer sees (1/k) x the sum of their gradients, and the
+non-finite test, the global-norm clip and the optimizer step run once per window, after its last micro-batch.  The last
+batch of an epoch closes its window early (the scale stays 1/k).  `global_step`, `fit(max_steps=...)`, the non-finite
+poller and `ShadowAdam.calls` count OPTIMIZER STEPS.  k = 1 (the default) is the unaccumulated step, launch for
+launch."""
 
 import json
 import os
@@ -15,8 +22,17 @@ from . import nonfinite as NF
 
 class Trainer:
     def __init__(self, cfg, device="cuda", precision=None, dist_ctx=None, log_path=None, miopen_benchmark=False,
-                 sync_bn=False, flat_optimizer=None, graph_image_encoder=None, graph_text_encoder=None, nonfinite=None):
+                 sync_bn=False, flat_optimizer=None, graph_image_encoder=None, graph_text_encoder=None, nonfinite=None,
+                 accumulate_grad_batches=None):
         self.cfg = cfg
+        # micro-batches per optimizer step: the argument overrides cfg.lightning.trainer.accumulate_grad_batches
+        k = accumulate_grad_batches if accumulate_grad_batches is not None else cfg.lightning.trainer.accumulate_grad_batches
+        if k is None:
+            k = 1
+        if isinstance(k, bool) or not isinstance(k, int) or k < 1:
+            raise ValueError(f"accumulate_grad_batches must be an integer >= 1, got {k!r}")
+        self.accumulate = k
+        self._micro = 0                   # micro-batches already in the open window (0: no window is open)
         self.device = torch.device(device)
         prec = precision if precision is not None else cfg.lightning.trainer.precision
         self.autocast_dtype = torch.bfloat16 if str(prec) in ("16", "bf16") else None
@@ -111,6 +127,8 @@ class Trainer:
         self.cfg.set_path("train.optimizer.flat_clip", self.clip if self.flat_optimizer else None)
         self.cfg.set_path("train.optimizer.flat_grads",
                           bool(self.flat_optimizer and self.dist is not None and self.dist.active))
+        # accumulation windows: fp32 flat accumulators in every group, filled by glr_accum_mt (gloria/optim.py)
+        self.cfg.set_path("train.optimizer.flat_accumulate", self.accumulate if self.flat_optimizer else 1)
         opt = model.configure_optimizers()
         self.optimizer, self.scheduler = opt["optimizer"], opt["lr_scheduler"]
         self.params = [p for g in self.optimizer.param_groups for p in g["params"]]
@@ -218,7 +236,10 @@ class Trainer:
         return out
 
     # ------------------------------------------------------------------ one optimisation step
-    def training_step(self, model, batch, batch_idx=0):
+    def training_step(self, model, batch, batch_idx=0, last_in_epoch=False):
+        """one micro-batch: forward, backward and - when it closes its accumulation window (every batch with
+        accumulate_grad_batches = 1; else the window's k-th batch, or the epoch's last one) - the optimizer step.
+        Returns the micro-batch's own, undivided loss."""
         batch = self.to_device(batch)
         if not self._graph_tried and self.device.type == "cuda" and self.autocast_dtype is not None:
             self._graph_tried = True          # once: the batch shape is static in training (drop_last loaders)
@@ -232,13 +253,35 @@ class Trainer:
         with ctx:
             out = model.training_step(batch, batch_idx)
         loss = out["loss"]
-        if self.reducer is not None:
-            self.reducer.zero_grad()
-            loss.backward()                   # bucket all-reduces start as soon as a bucket is complete
-            self.reducer.finish()
+        k = self.accumulate
+        if k == 1:
+            if self.reducer is not None:
+                self.reducer.zero_grad()
+                loss.backward()               # bucket all-reduces start as soon as a bucket is complete
+                self.reducer.finish()
+            else:
+                self.optimizer.zero_grad(set_to_none=True)
+                loss.backward()
         else:
-            self.optimizer.zero_grad(set_to_none=True)
-            loss.backward()
+            first = self._micro == 0
+            last = self._micro + 1 == k or bool(last_in_epoch)
+            self._micro = 0 if last else self._micro + 1
+            # flat optimizer: backward at the full loss (the micro-batch's gradients are bitwise those of an
+            # unaccumulated step) and 1/k applied in fp32 on the way into the accumulator; stock: the loss is divided
+            # and autograd adds in place
+            part = loss if self.flat else loss / k
+            if self.reducer is not None:
+                self.reducer.begin(first, last, scale=1.0 / k)
+                part.backward()
+                self.reducer.finish()         # the all-reduce happens in the window's last cycle only
+            else:
+                if first or self.flat:
+                    self.optimizer.zero_grad(set_to_none=True)
+                part.backward()
+                if self.flat:
+                    self.optimizer.accumulate(1.0 / k, first)
+            if not last:
+                return self._global_loss(model, loss)
         run = True if self.flat else self._stock_guard()       # the flat optimizer guards inside its step
         if self.clip and not self.flat:       # the flat optimizer clips inside its step (post-reduce global norm)
             torch.nn.utils.clip_grad_norm_(self.params, self.clip)
@@ -278,8 +321,8 @@ class Trainer:
         for epoch in range(self.max_epochs):
             model.current_epoch = epoch
             t0 = time.time()
-            for i, batch in enumerate(dm.train_dataloader()):
-                loss = self.training_step(model, batch, i)
+            for i, (batch, last) in enumerate(_mark_last(dm.train_dataloader())):
+                loss = self.training_step(model, batch, i, last_in_epoch=last)
                 history.append(float(loss))
                 self._log({"step": self.global_step, "epoch": epoch, "train_loss": history[-1]})
                 if max_steps is not None and self.global_step >= max_steps:
@@ -303,6 +346,8 @@ class Trainer:
 
     # ------------------------------------------------------------------ checkpoints (reference layout + resume state)
     def save_checkpoint(self, model, path):
+        """Checkpoints are written at epoch ends, where no accumulation window is open (the epoch's last batch closes
+        it): gradient accumulators are not saved, and a resumed run starts a new window."""
         self._poll_nonfinite(now=True)
         os.makedirs(os.path.dirname(path) or ".", exist_ok=True)
         ckpt = model.checkpoint()
@@ -341,6 +386,19 @@ class Trainer:
             else:
                 r[NF.APPLIED] = int(nf["applied"])
             self.monitor.seen_skipped = int(nf["skipped"])
+
+
+def _mark_last(loader):
+    """(batch, is the last one) over a loader, by a one-batch look-ahead (no len(): iterable datasets have none)"""
+    it = iter(loader)
+    try:
+        cur = next(it)
+    except StopIteration:
+        return
+    for nxt in it:
+        yield cur, False
+        cur = nxt
+    yield cur, True
 
 
 class _Snapshot:

@@ -618,6 +618,16 @@ int glr_selftest_quotient(int d_lo, int d_hi, uint64_t* bad, void* stream);
  * `flat` (element offsets = the table's flat offsets), one launch: how a data-parallel rank fills an all-reduce bucket
  * when the bucket's last gradient has arrived. */
 int glr_gather_mt(const void* chunk_table, int n_chunks, const uint64_t* grad_ptrs, int dtype, void* flat, void* stream);
+/* glr_accum_mt: gradient accumulation over micro-batches into an fp32 flat accumulator `acc` (the chunk table and
+ * pointer table of glr_gather_mt, one workgroup of 256 threads per entry; src_dtype = element type of the gradients).
+ * Per element of a chunk, g widened to fp32:  first != 0: acc[foff + i] = scale * g;  first == 0: acc[foff + i] =
+ * fmaf(scale, g, acc[foff + i]) - one rounding either way.  A parameter whose pointer is 0: first != 0 writes zeros to
+ * its slot (the previous window's sums go without a memset), first == 0 leaves it alone.  Nothing outside
+ * [foff, foff + count) is written (the padding between parameters keeps its zeros).  inf / NaN survive the additions:
+ * the guarded sum of squares over `acc` is the window's non-finite test.  GLR_EINVAL: a null pointer, n_chunks <= 0 or
+ * a scale that is not finite. */
+int glr_accum_mt(const void* chunk_table, int n_chunks, const uint64_t* grad_ptrs, int src_dtype, float* acc, float scale,
+                 int first, void* stream);
 int glr_sumsq_mt(const void* chunk_table, int n_chunks, const uint64_t* grad_ptrs, int dtype, float* partial,
                  void* stream);
 int glr_adam_step_mt(const void* chunk_table, int n_chunks, const uint64_t* grad_ptrs, int grad_dtype, float* master,
