@@ -81,6 +81,27 @@ __device__ __forceinline__ float wave_max(float v) {
   return v;
 }
 
+// Philox4x32-10: the dropout generator of the streaming epilogues (glr_lnorm.hip, glr_ffn.hip); counter c0..c3, key k0, k1
+struct U4 { unsigned x, y, z, w; };
+__device__ __forceinline__ U4 philox4x32(unsigned c0, unsigned c1, unsigned c2, unsigned c3, unsigned k0, unsigned k1) {
+#pragma unroll
+  for (int r = 0; r < 10; ++r) {
+    const unsigned hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
+    const unsigned hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
+    c0 = hi1 ^ c1 ^ k0; c1 = lo1; c2 = hi0 ^ c3 ^ k1; c3 = lo0;
+    k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
+  }
+  return {c0, c1, c2, c3};
+}
+// four bf16 of one 8-byte load <-> fp32
+__device__ __forceinline__ void unpack4(const uint2 u, float (&f)[4]) {
+  f[0] = __uint_as_float(u.x << 16); f[1] = __uint_as_float(u.x & 0xffff0000u);
+  f[2] = __uint_as_float(u.y << 16); f[3] = __uint_as_float(u.y & 0xffff0000u);
+}
+__device__ __forceinline__ uint2 pack4(const float (&f)[4]) {
+  return make_uint2((unsigned)f2bf(f[0]) | ((unsigned)f2bf(f[1]) << 16), (unsigned)f2bf(f[2]) | ((unsigned)f2bf(f[3]) << 16));
+}
+
 // Operand traits of the two arithmetic modes of the MFMA kernels.
 //   F32 : fp32 operands, v_mfma_f32_32x32x2_f32 (exact fp32 fma chain) - the 1e-4 parity mode
 //   BF16: bf16 operands, v_mfma_f32_32x32x16_bf16, fp32 accumulate

@@ -91,6 +91,11 @@ SYMBOLS = {
     "glr_type_embedding_bwd": (c_int, [c_void_p, c_void_p, ctypes.c_longlong, c_int, c_void_p, c_void_p, c_void_p]),
     "glr_colsum_workspace_floats": (c_int, [ctypes.c_longlong, c_int]),
     "glr_colsum_bf16": (c_int, [c_void_p, ctypes.c_longlong, c_int, c_void_p, c_void_p, c_int, c_void_p]),
+    "glr_ffn_workspace_floats": (c_int, [ctypes.c_longlong, c_int]),
+    "glr_relu_drop_fwd": (c_int, [c_void_p, ctypes.c_longlong, c_int, c_float, ctypes.c_ulonglong, ctypes.c_ulonglong, c_void_p,
+                                  c_void_p, c_void_p, c_void_p]),
+    "glr_relu_drop_bwd": (c_int, [c_void_p, c_void_p, ctypes.c_longlong, c_int, c_float, c_void_p, c_void_p, c_void_p, c_int,
+                                  c_void_p]),
     "glr_attn_max_tokens": (c_int, [c_int]),
     "glr_attn_fwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_float, c_float,
                              ctypes.c_ulonglong, ctypes.c_ulonglong, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),

@@ -121,7 +121,11 @@ def _pack_operands(img_features, words, no_attn_vec, cap_lens, o):
     vt_t = torch.empty_like(vt)
     N.check(L.glr_pack_regions_tiled(N.ptr(img), in_code, layout, N.ptr(na), N.ptr(vt), N.ptr(vt_t), B, D, S, code, st),
             "glr_pack_regions_tiled")
-    gram = torch.bmm(vt, vt.transpose(1, 2))            # plain batched GEMM (hipBLASLt): G[b] = V^T V
+    # plain batched GEMM (hipBLASLt): G[b] = V^T V in the OPERAND dtype.  Outside autocast: fp32 operands under bf16 autocast
+    # (fp32 image embeddings from the region transformer + the fp32 word embeddings) would come back as a bf16 gram of
+    # half the bytes glr_tile_gram reads and writes for `code`
+    with torch.autocast("cuda", enabled=False):
+        gram = torch.bmm(vt, vt.transpose(1, 2))
     gram_t = torch.empty_like(gram)
     # tiling + the ones row (a padded region) out of which the forward pair kernel reads Z_w = sum_r e2[w, r]
     # (include/glr.h, tile_rowflags); every kernel masks padded regions, so nothing else sees the row

@@ -22,6 +22,7 @@ import torch.nn as nn
 from .. import builder
 from .. import loss
 from ..loss import gloria_loss as GL
+from . import image_transformer
 
 
 class PositionEmbeddings(nn.Module):
@@ -168,12 +169,12 @@ class GLoRIA(nn.Module):
         img_feat_g, img_emb_l = self.img_encoder(imgs, get_local=True)
         img_emb_g, img_emb_l = self.img_encoder.generate_embeddings(img_feat_g, img_emb_l)
         b, c, h, w = img_emb_l.shape
-        if self.position_embeddings is not None:
-            pos = self.position_embeddings((h, w)).permute(2, 0, 1).expand(b, c, h, w)
-            img_emb_l = img_emb_l + pos
+        pos = self.position_embeddings((h, w)) if self.position_embeddings is not None else None       # [h, w, c]
         if self.image_transformer is not None:
-            flat = img_emb_l.reshape(b, c, h * w).permute(2, 0, 1)
-            img_emb_l = self.image_transformer(flat).permute(1, 2, 0).reshape(b, c, h, w)
+            # the region transformer on the HIP path where it applies, the stock module elsewhere (models/image_transformer.py)
+            img_emb_l = image_transformer.run(self.image_transformer, img_emb_l, None if pos is None else pos.reshape(h * w, c))
+        elif pos is not None:
+            img_emb_l = img_emb_l + pos.permute(2, 0, 1).expand(b, c, h, w)
         return img_emb_l, img_emb_g
 
     # ------------------------------------------------------------------ losses (ref :105-150)

@@ -365,7 +365,8 @@ class ShadowAdam(torch.optim.Optimizer):
 
 
 def shadow_parameter_ids(model):
-    """parameters autocast would cast to bf16 on every use: those of Linear / Conv modules (weights and biases).
+    """parameters autocast would cast to bf16 on every use: those of Linear / Conv modules (weights and biases) and the
+    packed input projection of an nn.MultiheadAttention (the image-region transformer: 1.8 M values per layer).
     Normalisation layers, free-standing parameters and EMBEDDINGS stay fp32: autocast leaves F.embedding alone, and
     the position / token-type rows collect hundreds of gradient contributions per step, which a bf16 gradient buffer
     would sum at 8 bits."""
@@ -373,4 +374,6 @@ def shadow_parameter_ids(model):
     for m in model.modules():
         if isinstance(m, (torch.nn.Linear, torch.nn.Conv2d)):
             ids.update(id(p) for p in m.parameters(recurse=False))
+        elif isinstance(m, torch.nn.MultiheadAttention):
+            ids.update(id(p) for p in (m.in_proj_weight, m.in_proj_bias) if p is not None)
     return ids

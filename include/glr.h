@@ -493,6 +493,31 @@ int glr_colsum_workspace_floats(long long R, int C);
 int glr_colsum_bf16(const void* x16, long long R, int C, float* workspace, void* out, int out_bf16, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Feed-forward middle of a post-LN transformer encoder layer,  a = dropout(relu(z)),  of the image-region transformer
+ * (reference: the nn.TransformerEncoder of gloria/models/gloria_model.py:52-59, run under native AMP), one HBM pass per
+ * direction (csrc/glr_ffn.hip).
+ *   z16    bf16 [R, C] contiguous: the output of linear1, bias included;  C % 256 == 0, C <= 4096, R >= 1 (64-bit rows)
+ *   a16    bf16 [R, C]: bf16_rne(max(float(z), 0) * s) where the element is kept, else +0;  s = 1.0f / (1.0f - p_drop) in
+ *          fp32 on the host (p_drop == 0: s = 1 and nothing is drawn)
+ *   alive  u64 [R, C/64], one bit per element, `kept && z > 0`, in the layout of glr_drop_add_ln_fwd's mask (element
+ *          4 (l + 64 i) + c of a row = bit l of word 4 i + c).  NULL: nothing is stored - the no-grad / eval call, legal
+ *          only with p_drop == 0
+ *   seed / offset / rng_cell   Philox4x32-10 key (seed, offset) or (rng_cell[0], rng_cell[1] + offset), counter
+ *          r * (C / 4) + quad as glr_drop_add_ln_fwd: the mask is a pure function of (key, row, column), not of R or the
+ *          launch geometry
+ * bwd: dy16 bf16 [R, C] and `alive` in;  dz16 = bf16_rne(float(dy) * s) where alive, else +0 (z is not an input);
+ *      dzsum (NULL = not wanted): column sums of the ROUNDED dz16 values, fp32 accumulation in a fixed two-level order, fp32
+ *      or bf16 [C] (dzsum_bf16) - the bias gradient of linear1;  workspace: glr_ffn_workspace_floats(R, C) floats (0 = shape
+ *      not supported; only read and written when dzsum is given).  No atomics: bitwise reproducible.
+ * Bad shapes / rates return GLR_EINVAL and launch nothing.  HBM traffic 4 bytes + 1 bit per element each way.
+ */
+int glr_ffn_workspace_floats(long long R, int C);
+int glr_relu_drop_fwd(const void* z16, long long R, int C, float p_drop, unsigned long long seed, unsigned long long offset,
+                      const unsigned long long* rng_cell, void* a16, unsigned long long* alive, void* stream);
+int glr_relu_drop_bwd(const void* dy16, const unsigned long long* alive, long long R, int C, float p_drop, void* dz16,
+                      float* workspace, void* dzsum, int dzsum_bf16, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Self-attention of the BERT text encoder for short captions (reference: BertSelfAttention of
  * transformers' BertModel, gloria/models/text_model.py:18-20; 97 tokens in imagenome_pretrain_config.yaml):
  *   O = dropout(softmax(Q K^T * scale + key mask)) V      per (sentence, head), head size 64, L <= 128 tokens.
