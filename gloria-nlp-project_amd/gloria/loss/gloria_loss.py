@@ -13,25 +13,28 @@ Differences that are deliberate and documented in DESIGN.md:
   * `local_loss` forms the whole B x B similarity matrix in ONE launch; nothing of size
     O(B * |img_features|) is kept for backward (the reference keeps one transposed copy per
     sentence).
+
+K1 (the fused local-attention kernels) has two callers with one autograd function each: `LocalSimFn` behind
+`local_similarity` (forward and backward in HIP) and `PairAttnFn` behind `attention_fn` (K1 forward in pair
+mode; the gradient of its B small pairs is a torch restatement).  They share `_pack_operands` and `_k1_forward`.
 """
 
-from typing import List, Optional, Sequence
+from collections import namedtuple
+from typing import Callable, List, Optional, Sequence
 
 import numpy as np
 
 import torch
 
 from .. import _native as N
-from . import _recompute as R
 
-_COMPUTE_DTYPE = None          # None = follow the input dtype
+_COMPUTE_DTYPE = None         # None = follow the input dtype
 # bench.py sets this to {} to collect HIP events on the launch stream (the stream torch's events record on is the
 # stream libglr launches on: N.stream()).  Keys -> lists of (event, event):
 #   "k1_fwd"     the K1 forward launches alone               "k1_fwd_op"  packing + Gram + tiling + K1 forward
 #   "k1_bwd"     the K1 backward launch alone                "k1_bwd_op"  K1 backward + gradient GEMMs + scatter
 # and "k1_flops": algorithmic forward FLOPs of every forward call.
 PROFILE = None
-_DEBUG_HOOK = None          # diagnostics only: called with the K1 backward outputs (tools)
 
 
 class _Range:
@@ -74,21 +77,24 @@ def _as_supported(t):
     return t.float().contiguous()      # fp16 / fp64 inputs are computed in fp32
 
 
+def _k1_inputs(img_features, words_emb):
+    """detached inputs of both K1 autograd functions; channels-last images of a supported dtype stay as they are"""
+    img = img_features.detach()
+    return (img if img.dtype in (torch.float32, torch.bfloat16) else _as_supported(img)), _as_supported(words_emb.detach())
+
+
 # ------------------------------------------------------------------------------------------
-# fused local similarity (K1) as an autograd function
+# fused local attention (K1): one autograd function per caller
 # ------------------------------------------------------------------------------------------
 
-class _Opts:
-    def __init__(self, temp1, temp2, temp3, agg, eps, want_attn, img_offset, word_start, pair_only, want_wctx,
-                 want_amean=False):
-        self.temp1, self.temp2, self.temp3 = float(temp1), float(temp2), float(temp3)
-        self.agg, self.eps = agg, float(eps)
-        self.want_attn, self.img_offset, self.word_start = want_attn, int(img_offset), int(word_start)
-        self.pair_only, self.want_wctx, self.want_amean = pair_only, want_wctx, want_amean
+_Opts = namedtuple("_Opts", "temp1 temp2 temp3 agg eps want_attn img_offset word_start want_amean", defaults=(False,))
+# what K1 reads: the tile plan, the MFMA operand dtype code, packed regions / Gram / words (`_t`: the K-tiled copies the
+# kernels stream; the row-major vt / tp stay for the gradient GEMMs) and the region counts
+_Operands = namedtuple("_Operands", "plan code vt vt_t gram_t tp tp_t tnorm s_eff s_pad shift")
 
 
-def _pack_operands(img_features, words, no_attn_vec, cap_lens, o):
-    """Operand packing shared by forward and backward: vt, gram, tp, tnorm + the tile plan."""
+def _pack_operands(img_features, words, no_attn_vec, cap_lens, word_start=0):
+    """Operand packing: vt, gram, tp, tnorm + the tile plan, as an _Operands record."""
     L = N.lib()
     dev = img_features.device
     B, D = img_features.shape[:2]
@@ -133,108 +139,91 @@ def _pack_operands(img_features, words, no_attn_vec, cap_lens, o):
     tp = torch.empty(plan.n_slots, D, dtype=odt, device=dev)
     tnorm = torch.empty(plan.n_slots, dtype=torch.float32, device=dev)
     N.check(L.glr_pack_words(N.ptr(words), in_code, N.ptr(plan.sent_slot0), N.ptr(plan.cap_lens), N.ptr(tp),
-                             N.ptr(tnorm), words.shape[0], D, words.shape[2], o.word_start, plan.n_slots,
+                             N.ptr(tnorm), words.shape[0], D, words.shape[2], word_start, plan.n_slots,
                              plan.capacity, code, st), "glr_pack_words")
     tp_t = torch.empty_like(tp)
     N.check(L.glr_tile_k(N.ptr(tp), N.ptr(tp_t), N.TILE_WORDS, plan.n_tiles, D * vt.element_size(), st), "glr_tile_k")
-    return plan, code, vt, vt_t, gram_t, tp, tp_t, tnorm, s_eff, s_pad, shift
+    return _Operands(plan, code, vt, vt_t, gram_t, tp, tp_t, tnorm, s_eff, s_pad, shift)
 
 
-def _k1_args(plan, vt, gram, tp, tnorm, B, D, s_eff, o):
-    return (N.ptr(vt), N.ptr(gram), N.ptr(tp), N.ptr(tnorm), plan.host.ctypes.data, N.ptr(plan._dev), B, D, s_eff,
-            o.temp1, o.temp2, o.temp3, N.AGG[o.agg], o.eps)
+def _k1_args(p, B, D, o):
+    return (N.ptr(p.vt_t), N.ptr(p.gram_t), N.ptr(p.tp_t), N.ptr(p.tnorm), p.plan.host.ctypes.data, N.ptr(p.plan._dev),
+            B, D, p.s_eff, o.temp1, o.temp2, o.temp3, N.AGG[o.agg], o.eps)
+
+
+def _k1_forward(p, o, B, D, sim, pair_only, n_words, lse=None, wstat=None, attn=None, attn_off=None, strip=0, amean=None,
+                a1buf=None):
+    """The K1 forward launch of both autograd functions; every image attends with `n_words` words (FLOP record)."""
+    with _Range("k1_fwd"):
+        N.check(N.lib().glr_local_attn_fwd(*_k1_args(p, B, D, o), N.ptr(sim), p.plan.n_sent, N.ptr(lse), N.ptr(wstat),
+                                           N.ptr(attn), N.ptr(attn_off), strip, pair_only, o.img_offset, N.ptr(amean),
+                                           N.ptr(a1buf), p.code, N.stream()), "glr_local_attn_fwd")
+    if PROFILE is not None:
+        PROFILE.setdefault("k1_flops", []).append((4.0 * p.s_eff * D + 6.0 * D) * B * n_words)
 
 
 class LocalSimFn(torch.autograd.Function):
-    """sim[b, i] for local images x all sentences (+ diagonal attention maps, + word-mean attention rows).
-    HIP forward (K1) and HIP backward (K1 bwd + three plain GEMMs), including the gradients that arrive
-    through the diagonal attention maps (attention-supervision loss) and through the word-mean rows
-    (regularisers).  Only the standalone attention_fn outputs (pair mode: maps + weighted context of B
-    pairs) are differentiated through the torch restatement in loss/_recompute.py."""
+    """(sim, attn, amean): sim[b, i] for local images x all sentences, the flat diagonal attention maps and the
+    word-mean attention rows (empty tensors where not asked for).  HIP forward (K1) and HIP backward (K1 bwd +
+    three plain GEMMs), including the gradients that arrive through the diagonal attention maps
+    (attention-supervision loss) and through the word-mean rows (regularisers)."""
 
     @staticmethod
     def forward(ctx, img_features, words_emb, no_attn_vec, cap_lens, opts):
         N.require_cuda(img_features, words_emb, no_attn_vec)
-        L = N.lib()
         o = opts
-        img = _as_supported(img_features.detach()) if img_features.dtype not in (torch.float32, torch.bfloat16) \
-            else img_features.detach()
-        words = _as_supported(words_emb.detach())
-        op_range = _Range("k1_fwd_op")
-        op_range.__enter__()
-        plan, code, vt, vt_t, gram_t, tp, tp_t, tnorm, s_eff, s_pad, shift = _pack_operands(img, words, no_attn_vec, cap_lens, o)
-        dev = img.device
-        B, D = img.shape[:2]
-        n_sent = plan.n_sent
-        need_grad = any(t is not None and t.requires_grad for t in (img_features, words_emb, no_attn_vec)) \
-            and not o.pair_only
-        sim = (torch.zeros if o.pair_only else torch.empty)(B, n_sent, dtype=torch.float32, device=dev)
-        lse = torch.empty(B, n_sent, s_pad, dtype=torch.float32, device=dev) if need_grad else None
-        wstat = torch.empty(B, plan.n_slots, 4, dtype=torch.float32, device=dev) if need_grad else None
-        attn = attn_off = None
-        strip = 0 if o.want_wctx else shift
-        if o.want_attn:
-            attn_off, off_host = plan.attn_offsets(s_eff - strip, dev)
-            attn = torch.zeros(int(off_host[-1]), dtype=torch.float32, device=dev)
-        amean = torch.empty(B, n_sent, s_pad, dtype=torch.float32, device=dev) if o.want_amean else None
-        # the forward pair kernels hand the word-softmax values to the backward pair kernel (98 KB per image x pair, fp16,
-        # in the kernels' own register order): the backward has no score stream of its own
-        a1buf = None
-        if need_grad and plan.n_pair:
-            a1buf = torch.empty(B * plan.n_pair * 24576, dtype=torch.int32, device=dev)
-        with _Range("k1_fwd"):
-            N.check(L.glr_local_attn_fwd(*_k1_args(plan, vt_t, gram_t, tp_t, tnorm, B, D, s_eff, o), N.ptr(sim), n_sent,
-                                         N.ptr(lse), N.ptr(wstat), N.ptr(attn), N.ptr(attn_off), strip,
-                                         1 if o.pair_only else 0, o.img_offset, N.ptr(amean), N.ptr(a1buf), code, N.stream()),
-                    "glr_local_attn_fwd")
-        op_range.__exit__()
-        if PROFILE is not None:
-            n_words = plan.n_words if not o.pair_only else plan.n_words // max(n_sent, 1)
-            PROFILE.setdefault("k1_flops", []).append((4.0 * s_eff * D + 6.0 * D) * B * n_words)
-        wctx = None
-        if o.want_wctx:      # attention_fn's first output: V . a2^T for the B diagonal pairs (plain bmm)
-            n = int(plan.cap_lens_host[0])
-            a2 = attn.view(B, n, s_eff)
-            wctx = torch.bmm(a2.to(vt.dtype), vt[:, :s_eff]).transpose(1, 2).float().contiguous()   # [B, D, n]
-            attn = a2[:, :, shift:].contiguous().view(-1)
-        ctx.save_for_backward(img_features, words_emb, no_attn_vec, vt, vt_t, gram_t, tp, tp_t, tnorm, sim, lse, wstat, a1buf)
-        ctx.plan, ctx.opts, ctx.meta = plan, o, (code, s_eff, s_pad, shift)
-        ctx.set_materialize_grads(False)       # unused outputs (maps, context) arrive as None
-        if attn is None:
-            attn = sim.new_zeros(0)
-        if wctx is None:
-            wctx = sim.new_zeros(0)
-        if amean is None:
-            amean = sim.new_zeros(0)
-        return sim, attn, wctx, amean
-
-    @staticmethod
-    def backward(ctx, dsim, dattn, dwctx, damean):
-        img_features, words_emb, no_attn_vec, vt, vt_t, gram_t, tp, tp_t, tnorm, sim, lse, wstat, a1buf = ctx.saved_tensors
-        plan, o = ctx.plan, ctx.opts
-        code, s_eff, s_pad, shift = ctx.meta
-        L = N.lib()
         dev = img_features.device
         B, D = img_features.shape[:2]
-        d_img = None              # allocated by whoever contributes first (the common case needs no fp32 staging at all)
+        f32 = dict(dtype=torch.float32, device=dev)
+        img, words = _k1_inputs(img_features, words_emb)
+        with _Range("k1_fwd_op"):
+            p = _pack_operands(img, words, no_attn_vec, cap_lens, o.word_start)
+            plan, n_sent = p.plan, p.plan.n_sent
+            need_grad = any(t is not None and t.requires_grad for t in (img_features, words_emb, no_attn_vec))
+            sim = torch.empty(B, n_sent, **f32)
+            lse = torch.empty(B, n_sent, p.s_pad, **f32) if need_grad else None
+            wstat = torch.empty(B, plan.n_slots, 4, **f32) if need_grad else None
+            attn = attn_off = None
+            if o.want_attn:
+                attn_off, off_host = plan.attn_offsets(p.s_eff - p.shift, dev)
+                attn = torch.zeros(int(off_host[-1]), **f32)
+            amean = torch.empty(B, n_sent, p.s_pad, **f32) if o.want_amean else None
+            # the forward pair kernels hand the word-softmax values to the backward pair kernel (98 KB per image x pair,
+            # fp16, in the kernels' own register order): the backward has no score stream of its own
+            a1buf = None
+            if need_grad and plan.n_pair:
+                a1buf = torch.empty(B * plan.n_pair * 24576, dtype=torch.int32, device=dev)
+            _k1_forward(p, o, B, D, sim, 0, plan.n_words, lse, wstat, attn, attn_off, p.shift, amean, a1buf)
+        ctx.save_for_backward(img_features, words_emb, no_attn_vec, sim, lse, wstat, a1buf,
+                              p.vt, p.vt_t, p.gram_t, p.tp, p.tp_t, p.tnorm)
+        ctx.plan, ctx.opts, ctx.meta = plan, o, (p.code, p.s_eff, p.s_pad, p.shift)
+        ctx.set_materialize_grads(False)       # unused outputs (maps, word-mean rows) arrive as None
+        return sim, sim.new_zeros(0) if attn is None else attn, sim.new_zeros(0) if amean is None else amean
+
+    @staticmethod
+    def backward(ctx, dsim, dattn, damean):
+        img_features, words_emb, no_attn_vec, sim, lse, wstat, a1buf, vt, vt_t, gram_t, tp, tp_t, tnorm = ctx.saved_tensors
+        plan, o = ctx.plan, ctx.opts
+        code, s_eff, s_pad, shift = ctx.meta
+        dev = img_features.device
+        B, D = img_features.shape[:2]
         d_words = torch.zeros(words_emb.shape, dtype=torch.float32, device=dev)
         d_na = None if no_attn_vec is None else torch.zeros(D, dtype=torch.float32, device=dev)
 
+        # the gradients of the word-mean rows (regularisers) and of the diagonal attention maps (attention-supervision
+        # loss) go through K1 backward together with the gradient of sim
         have_dam = o.want_amean and damean is not None and damean.numel() > 0
-        need_attn = o.want_attn and dattn is not None and dattn.numel() > 0
-        need_wctx = o.want_wctx and dwctx is not None and dwctx.numel() > 0
-        # the gradient of the diagonal attention maps (attention-supervision loss) goes through K1 backward too;
-        # only attention_fn's own outputs (pair mode / weighted context) keep the torch restatement below
-        hip_attn = need_attn and not o.pair_only and not o.want_wctx
-        if (dsim is not None or have_dam or hip_attn) and not o.pair_only:
+        have_dat = o.want_attn and dattn is not None and dattn.numel() > 0
+        if dsim is None and not have_dam and not have_dat:          # nothing arrived from upstream
+            d_img = torch.zeros(img_features.shape, dtype=img_features.dtype, device=dev)
+        else:
             if lse is None:
                 raise RuntimeError("local similarity was computed without gradient state")
             if dsim is None:
                 dsim = torch.zeros_like(sim)
             dam = damean.float().contiguous() if have_dam else None
-            dat = dattn.float().contiguous() if hip_attn else None
-            strip = 0 if o.want_wctx else shift
-            dat_off = plan.attn_offsets(s_eff - strip, dev)[0] if hip_attn else None
+            dat = dattn.float().contiguous() if have_dat else None
+            dat_off = plan.attn_offsets(s_eff - shift, dev)[0] if have_dat else None
             odt = vt.dtype
             ns = plan.n_slots
             xout = torch.empty(ns, B, s_pad, dtype=odt, device=dev)
@@ -243,65 +232,89 @@ class LocalSimFn(torch.autograd.Function):
             gamma = torch.empty(B, ns, dtype=torch.float32, device=dev)
             beta = torch.empty(B, ns, dtype=torch.float32, device=dev)
             g = dsim.float().contiguous()
-            bwd_range = _Range("k1_bwd_op")
-            bwd_range.__enter__()
-            with _Range("k1_bwd"):
-                N.check(L.glr_local_attn_bwd(*_k1_args(plan, vt_t, gram_t, tp_t, tnorm, B, D, s_eff, o), N.ptr(sim),
-                                             N.ptr(g), plan.n_sent, N.ptr(lse), N.ptr(wstat), N.ptr(dam), N.ptr(dat),
-                                             N.ptr(dat_off), strip, o.img_offset, N.ptr(xout), N.ptr(aout), N.ptr(baout),
-                                             N.ptr(gamma), N.ptr(beta), N.ptr(a1buf), code, N.stream()), "glr_local_attn_bwd")
-            if _DEBUG_HOOK is not None:
-                _DEBUG_HOOK(xout, aout, baout, gamma, beta)
-            # gradient GEMMs (plain library GEMMs on the kernel's outputs)
-            x2d = xout.view(ns, B * s_pad)
-            dtp = (x2d @ vt.view(B * s_pad, D)).float() - gamma.sum(0).unsqueeze(1) * tp.float()      # [ns, D]
-            P = torch.bmm(baout.transpose(1, 2), aout)                                                 # [B, S, S], baout = beta a2
-            # dvt = X^T tp - P vt: the second product accumulates onto the first inside the GEMM (one rounding of the
-            # fp32 sum to the operand dtype instead of two rounded products subtracted by three elementwise passes)
-            dvt = torch.baddbmm((x2d.t() @ tp).view(B, s_pad, D), P, vt, alpha=-1.0)                   # [B, S, D]
-            si, wi, slot = plan.word_index(dev)
-            d_words.permute(0, 2, 1)[si, wi + o.word_start] = dtp[slot]
-            cl = (img_features.dim() == 4 and img_features.dtype == dvt.dtype and not img_features.is_contiguous()
-                  and img_features.is_contiguous(memory_format=torch.channels_last))
-            if cl and not (need_attn and not hip_attn) and not need_wctx:
-                # channels-last features ARE [B, S, D] in memory: the packed-region gradient, minus the no-attention row
-                # and the padding, is the feature gradient - a strided view, no transpose / zero-fill / cast pass
-                H_, W_ = img_features.shape[2], img_features.shape[3]
-                d_img = dvt[:, shift:s_eff].unflatten(1, (H_, W_)).permute(0, 3, 1, 2)
-            else:
-                d_img = dvt[:, shift:s_eff].transpose(1, 2).float()
-            if d_na is not None:
-                d_na += dvt[:, 0].float().sum(0)
-            bwd_range.__exit__()
-
-        need_attn = need_attn and not hip_attn
-        if need_attn or need_wctx:
-            # gradient through the attention maps of the B diagonal pairs (torch restatement, small)
-            img = img_features.detach().float().reshape(B, D, -1)
-            words = words_emb.detach().float().requires_grad_(True)
-            na = None if no_attn_vec is None else no_attn_vec.detach().float().requires_grad_(True)
-            with torch.enable_grad():
-                vc = img.clone().requires_grad_(True)
-                V = vc if na is None else torch.cat([na.view(1, D, 1).expand(B, D, 1), vc], 2)
-                lens = plan.cap_lens_host[o.img_offset:o.img_offset + B]
-                a2 = R.diag_attention(V, words[o.img_offset:o.img_offset + B], lens, o.word_start, o.temp1)
-                loss = 0.0
-                if need_attn:
-                    flat = torch.cat([a2[b, :int(lens[b]), shift:].reshape(-1) for b in range(B)])
-                    off0 = int((plan.cap_lens_host[:o.img_offset].astype(np.int64) * (s_eff - shift)).sum())
-                    loss = loss + (flat * dattn[off0:off0 + flat.numel()].float()).sum()
-                if need_wctx:
-                    ctxv = torch.einsum("bdr,bwr->bdw", V, a2)
-                    loss = loss + (ctxv * dwctx[:, :, :ctxv.shape[2]].float()).sum()
-                loss.backward()
-            d_img = vc.grad if d_img is None else d_img.float() + vc.grad
-            d_words += words.grad
-            if na is not None and na.grad is not None:
-                d_na += na.grad
-        if d_img is None:
-            d_img = torch.zeros(img_features.shape, dtype=img_features.dtype, device=dev)
+            p = _Operands(plan, code, vt, vt_t, gram_t, tp, tp_t, tnorm, s_eff, s_pad, shift)
+            with _Range("k1_bwd_op"):
+                with _Range("k1_bwd"):
+                    N.check(N.lib().glr_local_attn_bwd(*_k1_args(p, B, D, o), N.ptr(sim), N.ptr(g), plan.n_sent, N.ptr(lse),
+                                                       N.ptr(wstat), N.ptr(dam), N.ptr(dat), N.ptr(dat_off), shift,
+                                                       o.img_offset, N.ptr(xout), N.ptr(aout), N.ptr(baout), N.ptr(gamma),
+                                                       N.ptr(beta), N.ptr(a1buf), code, N.stream()), "glr_local_attn_bwd")
+                # gradient GEMMs (plain library GEMMs on the kernel's outputs)
+                x2d = xout.view(ns, B * s_pad)
+                dtp = (x2d @ vt.view(B * s_pad, D)).float() - gamma.sum(0).unsqueeze(1) * tp.float()      # [ns, D]
+                P = torch.bmm(baout.transpose(1, 2), aout)                                # [B, S, S], baout = beta a2
+                # dvt = X^T tp - P vt: the second product accumulates onto the first inside the GEMM (one rounding of the
+                # fp32 sum to the operand dtype instead of two rounded products subtracted by three elementwise passes)
+                dvt = torch.baddbmm((x2d.t() @ tp).view(B, s_pad, D), P, vt, alpha=-1.0)                   # [B, S, D]
+                si, wi, slot = plan.word_index(dev)
+                d_words.permute(0, 2, 1)[si, wi + o.word_start] = dtp[slot]
+                if (img_features.dim() == 4 and img_features.dtype == dvt.dtype and not img_features.is_contiguous()
+                        and img_features.is_contiguous(memory_format=torch.channels_last)):
+                    # channels-last features ARE [B, S, D] in memory: the packed-region gradient, minus the no-attention
+                    # row and the padding, is the feature gradient - a strided view, no transpose / zero-fill / cast pass
+                    H_, W_ = img_features.shape[2], img_features.shape[3]
+                    d_img = dvt[:, shift:s_eff].unflatten(1, (H_, W_)).permute(0, 3, 1, 2)
+                else:
+                    d_img = dvt[:, shift:s_eff].transpose(1, 2).float()
+                if d_na is not None:
+                    d_na += dvt[:, 0].float().sum(0)
         return (d_img.reshape(img_features.shape).to(img_features.dtype), d_words.to(words_emb.dtype),
                 None if d_na is None else d_na.to(no_attn_vec.dtype), None, None)
+
+
+def _pair_attention(V, words, temp1):
+    """Differentiable restatement of K1's attention for B pairs of equal length: V [B, D, S_eff] regions (the
+    no-attention column included), words [B, D, n] -> a2 [B, n, S_eff]."""
+    if not V.is_cuda:
+        raise RuntimeError("the attention_fn backward is GPU-only")
+    a1 = torch.softmax(torch.einsum("bdr,bdw->brw", V, words), dim=2)        # over words
+    return torch.softmax(a1 * temp1, dim=1).transpose(1, 2)                   # over regions
+
+
+class PairAttnFn(torch.autograd.Function):
+    """(wctx, attn) of attention_fn: K1 in pair mode (image b attends with query b, all queries n words long) + one
+    bmm for the weighted context.  Backward differentiates `_pair_attention`, B small pairs, with torch autograd."""
+
+    @staticmethod
+    def forward(ctx, context, query, no_attn_vec, temp1):
+        N.require_cuda(context, query, no_attn_vec)
+        dev = context.device
+        B, D, n = query.shape
+        o = _Opts(float(temp1), 1.0, 1.0, "sum", 1e-8, True, 0, 0)
+        img, words = _k1_inputs(context, query)
+        with _Range("k1_fwd_op"):
+            p = _pack_operands(img, words, no_attn_vec, [n] * B)
+            sim = torch.empty(B, B, dtype=torch.float32, device=dev)        # scratch: the kernel writes its diagonal
+            attn_off, off_host = p.plan.attn_offsets(p.s_eff, dev)
+            attn = torch.zeros(int(off_host[-1]), dtype=torch.float32, device=dev)
+            _k1_forward(p, o, B, D, sim, 1, n, attn=attn, attn_off=attn_off)
+        a2 = attn.view(B, n, p.s_eff)
+        wctx = torch.bmm(a2.to(p.vt.dtype), p.vt[:, :p.s_eff]).transpose(1, 2).float().contiguous()     # V . a2^T: [B, D, n]
+        ctx.save_for_backward(context, query, no_attn_vec)
+        ctx.temp1 = o.temp1
+        ctx.set_materialize_grads(False)       # an unused output arrives as None
+        return wctx, a2[:, :, p.shift:].contiguous().view(-1)
+
+    @staticmethod
+    def backward(ctx, dwctx, dattn):
+        context, query, no_attn_vec = ctx.saved_tensors
+        B, D, n = query.shape
+        vc = context.detach().float().reshape(B, D, -1).clone().requires_grad_(True)
+        words = query.detach().float().requires_grad_(True)
+        na = None if no_attn_vec is None else no_attn_vec.detach().float().requires_grad_(True)
+        leaves = [vc, words] + ([] if na is None else [na])
+        outs = []                              # (output, its upstream gradient) of the outputs that have one
+        with torch.enable_grad():
+            V = vc if na is None else torch.cat([na.view(1, D, 1).expand(B, D, 1), vc], 2)
+            a2 = _pair_attention(V, words, ctx.temp1)
+            if dattn is not None:
+                outs.append((a2[:, :, V.shape[2] - vc.shape[2]:], dattn.float().reshape(B, n, -1)))
+            if dwctx is not None:
+                outs.append((torch.einsum("bdr,bwr->bdw", V, a2), dwctx.float()))
+        grads = torch.autograd.grad([y for y, _ in outs], leaves, [g for _, g in outs]) if outs \
+            else [torch.zeros_like(t) for t in leaves]
+        return (grads[0].reshape(context.shape).to(context.dtype), grads[1].to(query.dtype),
+                None if na is None else grads[2].to(no_attn_vec.dtype), None)
 
 
 # ------------------------------------------------------------------------------------------
@@ -430,9 +443,8 @@ def attention_fn(query, context, temp1, no_attn_vec=None):
     """
     B, D, n = query.shape
     ih, iw = context.size(2), context.size(3)
-    opts = _Opts(temp1, 1.0, 1.0, "sum", 1e-8, True, 0, 0, True, True)
-    _, attn, wctx, _ = LocalSimFn.apply(context, query, no_attn_vec, [n] * B, opts)
-    return wctx[:, :, :n].to(query.dtype), attn.view(B, n, ih, iw).to(query.dtype)
+    wctx, attn = PairAttnFn.apply(context, query, no_attn_vec, temp1)
+    return wctx.to(query.dtype), attn.view(B, n, ih, iw).to(query.dtype)
 
 
 def global_loss(cnn_code, rnn_code, eps=1e-8, temp3=10.0):
@@ -448,8 +460,9 @@ def local_similarity(img_features, words_emb, cap_lens: Sequence[int], temp1=4.0
                      want_amean=False):
     """B_img x n_sent similarity matrix (already * temp3) + flat diagonal attention maps
     (+ with want_amean the word-mean attention rows [B_img, n_sent, S_pad] of ALL pairs, else None)."""
-    opts = _Opts(temp1, temp2, temp3, agg, eps, want_attn, img_offset, word_start, False, False, want_amean)
-    sim, attn, _, amean = LocalSimFn.apply(img_features, words_emb, no_attn_vec, [int(c) for c in cap_lens], opts)
+    opts = _Opts(float(temp1), float(temp2), float(temp3), agg, float(eps), want_attn, int(img_offset), int(word_start),
+                 want_amean)
+    sim, attn, amean = LocalSimFn.apply(img_features, words_emb, no_attn_vec, [int(c) for c in cap_lens], opts)
     return sim, attn, (amean if want_amean else None)
 
 
@@ -553,24 +566,36 @@ def split_attention_maps(attn_flat, cap_lens, ih, iw, first=0, count=None) -> Li
     return maps
 
 
+def local_loss_rows(
+    img_features, words_emb, cap_lens, temp1=4.0, temp2=5.0, temp3=10.0, agg="sum", no_attn_vec=None,
+    no_attn_loss_weight=None, attention_divergence_loss_weight=None, attention_entropy_loss_weight=None,
+    img_offset=0, gather_rows: Optional[Callable] = None
+):
+    """local_loss of a block of rows: the images are those of sentences [img_offset, img_offset + B_img) of ALL the
+    sentences `words_emb` / `cap_lens`, and `gather_rows` turns this block of similarity rows into the full square
+    matrix (None: the block is the matrix).  The regularisers are this block's share of the global-batch means."""
+    want_aux = (no_attn_loss_weight is not None or attention_divergence_loss_weight is not None
+                or attention_entropy_loss_weight is not None)
+    ih, iw = img_features.shape[2], img_features.shape[3]
+    cap_lens = [int(c) for c in cap_lens]
+    sim, attn, amean = local_similarity(img_features, words_emb, cap_lens, temp1, temp2, temp3, agg, no_attn_vec,
+                                        img_offset=img_offset, want_amean=want_aux)
+    loss0, loss1 = dual_cross_entropy(sim, None if gather_rows is None else gather_rows(sim), img_offset)
+    att_maps = split_attention_maps(attn, cap_lens, ih, iw, img_offset, img_features.shape[0])
+    no_attn_loss = kl_loss = entropy_loss = 0
+    if want_aux:
+        shift = 0 if no_attn_vec is None else 1
+        no_attn_loss, kl_loss, entropy_loss = attention_regularisers(
+            amean, ih * iw + shift, shift, img_offset, no_attn_loss_weight, attention_divergence_loss_weight,
+            attention_entropy_loss_weight)
+    return loss0, loss1, no_attn_loss, kl_loss, entropy_loss, att_maps
+
+
 def local_loss(
     img_features, words_emb, cap_lens, temp1=4.0, temp2=5.0, temp3=10.0, agg="sum", no_attn_vec=None,
     no_attn_loss_weight=None, attention_divergence_loss_weight=None, attention_entropy_loss_weight=None
 ):
     """Local region x word InfoNCE (ref :99-201).  Returns
     (loss0, loss1, no_attn_loss, kl_loss, entropy_loss, att_maps)."""
-    want_aux = (no_attn_loss_weight is not None or attention_divergence_loss_weight is not None
-                or attention_entropy_loss_weight is not None)
-    ih, iw = img_features.shape[2], img_features.shape[3]
-    cap_lens = [int(c) for c in cap_lens]
-    sim, attn, amean = local_similarity(img_features, words_emb, cap_lens, temp1, temp2, temp3, agg, no_attn_vec,
-                                        want_amean=want_aux)
-    loss0, loss1 = dual_cross_entropy(sim)
-    att_maps = split_attention_maps(attn, cap_lens, ih, iw)
-    no_attn_loss = kl_loss = entropy_loss = 0
-    if want_aux:
-        shift = 0 if no_attn_vec is None else 1
-        no_attn_loss, kl_loss, entropy_loss = attention_regularisers(
-            amean, ih * iw + shift, shift, 0, no_attn_loss_weight, attention_divergence_loss_weight,
-            attention_entropy_loss_weight)
-    return loss0, loss1, no_attn_loss, kl_loss, entropy_loss, att_maps
+    return local_loss_rows(img_features, words_emb, cap_lens, temp1, temp2, temp3, agg, no_attn_vec, no_attn_loss_weight,
+                           attention_divergence_loss_weight, attention_entropy_loss_weight)

@@ -53,7 +53,7 @@ def test_attention_fn_golden(golden, name):
 @pytest.mark.parametrize("name", list(gi.ATTN_CASES))
 def test_attention_fn_output_grads_golden(golden, name):
     """gradients of attention_fn's own outputs (weighted context + maps) against the reference's autograd:
-    LocalSimFn.backward's pair-mode branch (need_wctx / need_attn)"""
+    PairAttnFn.backward with both upstream gradients live"""
     gd = golden("attention_grad")
     q, ctx, temp1, na = gi.attn_inputs(name)
     tq, tc = g(q, True), g(ctx, True)
@@ -65,6 +65,40 @@ def test_attention_fn_output_grads_golden(golden, name):
     check(gd, f"attn_grad/{name}/grad_context", tc.grad, rtol=2e-3, atol=2e-5)
     if tna is not None:
         check(gd, f"attn_grad/{name}/grad_no_attn", tna.grad, rtol=2e-3, atol=2e-4)
+
+
+@pytest.mark.parametrize("which", ["weighted", "map"])
+@pytest.mark.parametrize("name", ["a1_tiny", "a3_noattn_n96"])
+def test_attention_fn_single_output_grads_vs_oracle(name, which):
+    """Backpropagate ONE of attention_fn's two outputs (the other reaches PairAttnFn.backward as None) and compare
+    the input gradients with fp64 autograd through the oracle, in the bands of
+    test_attention_fn_output_grads_golden; the forward is bit-identical without gradient tracking."""
+    q, ctx, temp1, na = gi.attn_inputs(name)
+    tq, tc = g(q, True), g(ctx, True)
+    tna = None if na is None else g(na, True)
+    outs = gl().attention_fn(tq, tc, temp1, no_attn_vec=tna)
+    with torch.no_grad():
+        quiet = gl().attention_fn(tq, tc, temp1, no_attn_vec=tna)
+    plain = gl().attention_fn(g(q), g(ctx), temp1, no_attn_vec=None if na is None else g(na))
+    for o, a, b in zip(outs, quiet, plain):
+        assert not a.requires_grad and not b.requires_grad
+        assert torch.equal(o, a) and torch.equal(o, b)
+    k = ("weighted", "map").index(which)
+    up = gi.attn_upstream(name, tuple(outs[0].shape), tuple(outs[1].shape))[k]
+    (outs[k] * g(up)).sum().backward()
+    rq, rc = torch.from_numpy(q).double().requires_grad_(True), torch.from_numpy(ctx).double().requires_grad_(True)
+    rna = None if na is None else torch.from_numpy(na).double().requires_grad_(True)
+    (orc().attention_fn(rq, rc, temp1, no_attn_vec=rna)[k] * torch.from_numpy(up).double()).sum().backward()
+    cases = [("grad_query", tq, rq, 2e-5), ("grad_context", tc, rc, 2e-5)]
+    if na is not None:
+        cases.append(("grad_no_attn", tna, rna, 2e-4))
+    errs = [(label, t.grad.double().cpu().numpy(), r.grad.numpy(), atol) for label, t, r, atol in cases]
+    for label, got, want, atol in errs:
+        d = np.abs(got - want)
+        print(f"[{name} {which}] {label}: max |d| / max |ref| = {d.max() / np.abs(want).max():.3e}, "
+              f"worst |d| / (atol + rtol |ref|) = {(d / (atol + 2e-3 * np.abs(want))).max():.3e}")
+    for label, got, want, atol in errs:
+        np.testing.assert_allclose(got, want, rtol=2e-3, atol=atol, err_msg=label)
 
 
 @pytest.mark.parametrize("name", [n for n, c in gi.LOCAL_CASES.items() if c["aux"] is None])

@@ -440,8 +440,8 @@ def test_bf16_sharded_gradients_are_as_close_to_fp64_as_the_unsharded_ones(name,
 
 def test_channels_last_features_give_bitwise_the_contiguous_rank():
     """Rank 1 of full_bf16 (D = 256) with the bf16 image tensor in channels_last - the layout the image encoder hands
-    over: the layout = 1 branch of glr_pack_regions_tiled and the strided d_img view of LocalSimFn.backward.  vt is
-    bit-identical, and the d_img route differs only by an exact bf16 -> fp32 -> bf16 round trip, so sim, maps and all
+    over: the layout = 1 branch of glr_pack_regions_tiled and the strided d_img view LocalSimFn.backward returns for
+    every channels-last input of the operand dtype.  vt is bit-identical, and the d_img route differs only by an exact bf16 -> fp32 -> bf16 round trip, so sim, maps and all
     three gradients equal the contiguous run bit for bit."""
     name, D, world, no_attn = "full_bf16", 256, 3, True
     dctx = _collected(name, D, world, no_attn)
@@ -544,14 +544,14 @@ def test_k1_forward_refuses_a_negative_image_offset(pair_only):
     cap_lens = [6, 6]
     img = torch.from_numpy(gi.normal(7601, B, D, 3, 3)).to(DEV)
     words = torch.from_numpy(gi.normal(7602, B, D, L_)).to(DEV)
-    o = GL._Opts(*sc.TEMPS, "sum", 1e-8, False, -1, 0, bool(pair_only), False)
-    plan, code, vt, vt_t, gram_t, tp, tp_t, tnorm, s_eff, s_pad, shift = GL._pack_operands(img, words, None, cap_lens, o)
+    o = GL._Opts(*sc.TEMPS, "sum", 1e-8, False, -1, 0)
+    p = GL._pack_operands(img, words, None, cap_lens, o.word_start)
+    plan = p.plan
     sim = torch.full((B, plan.n_sent), 42.0, device=DEV)
 
     def fwd(offset):
-        return N.lib().glr_local_attn_fwd(*GL._k1_args(plan, vt_t, gram_t, tp_t, tnorm, B, D, s_eff, o), N.ptr(sim),
-                                          plan.n_sent, None, None, None, None, 0, pair_only, offset, None, None, code,
-                                          N.stream())
+        return N.lib().glr_local_attn_fwd(*GL._k1_args(p, B, D, o), N.ptr(sim), plan.n_sent, None, None, None, None, 0,
+                                          pair_only, offset, None, None, p.code, N.stream())
     for offset in (-1, -B):
         assert fwd(offset) == -1                       # GLR_EINVAL
         torch.cuda.synchronize()
